@@ -4,10 +4,19 @@ BASELINE.json metric: "images/sec (whole node) ResNet-50 224x224 DDP at
 1/2/4/8 MI355X"; baseline = the reference's FLOP-normalised headline,
 4,337 R50@224-equivalent img/s for its whole 16-GPU job.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU. Under torch.distributed.run the ranks read
     RANK/WORLD_SIZE/MASTER_*; run bare, bench.py starts torch.distributed.run
     itself as a child process and forwards its output and exit code.)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+``--dump-outputs DIR`` also writes what the last timed step computed (the
+updated parameters, the BN running statistics, the loss / top-k counters; see
+_dump_outputs) as ``DIR/<name>.npy``. That step starts from the seeded initial
+weights again, so that its outputs depend on the arguments and on one step's
+rounding alone; the path, and the time per step, are those of a plain run.
+``--full`` adds what the headline figure does not need: two instrumented steps
+after the timed region for the bucket timeline (``comm_overlap``).
 
 Each timed step is a complete training step on the hand-written MI355X
 path: GPU normalisation of synthetic uint8 images -> HIP forward (MFMA
@@ -39,6 +48,58 @@ BASELINES = {("resnet50", 224): BASELINE_IMG_S, ("resnet18", 224): 9776.0, ("res
              ("resnet18", 448): 2444.0}
 _NAMES = {"resnet18": "ResNet-18", "resnet34": "ResNet-34", "resnet50": "ResNet-50", "resnet101": "ResNet-101",
           "resnet152": "ResNet-152"}
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, 48 MiB for the three parameter-sized arrays
+
+
+def _dump_outputs(path, model, arena, opt, counters, reproducible_grads) -> None:
+    """``--dump-outputs``: what the last timed step produced (from the seeded initial state, which main() puts
+    back in front of that step), as ``<path>/<name>.npy``.
+
+    Always written: ``parameters`` (the updated fp32 masters), ``bn_running_mean`` / ``bn_running_var``,
+    ``gradient_fc_bias`` and ``metrics`` (that step's loss sum / top-1 / top-5 / image counters, float64). On the
+    default path these repeat from run to run to 5e-3 of their norm or better; the gradients as a whole do not:
+    the BatchNorm statistics are summed with float atomics, bf16 rounding of the activations turns their last-bit
+    differences into a noise floor, and at random init the early layers' gradients are sums of cancelling terms
+    (one step twice from one state: loss 2e-4 apart, BN statistics 4e-4, fc.bias's gradient 5e-4, fc.weight's
+    5 %, layer 1's 100 %; profiles/bench_dump_repeatability.md, scripts/step_repeatability.py). ``gradients`` and
+    ``momentum`` are therefore written only with ``--deterministic 1`` (``reproducible_grads``), where they repeat
+    to 5e-7.
+
+    Parameter-sized arrays are the arena's flat fp32 buffers gathered in ``model.named_parameters()`` order
+    (independent of the bucket layout); an array longer than DUMP_MAX_ELEMS is reduced to a fixed sample of that
+    many elements (sorted indices from a generator seeded with the array length, the same in every run and every
+    build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t, dtype=torch.float32):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(t.numel())
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to("cpu", dtype).numpy())
+
+    def gather(flat):
+        return torch.cat([arena.flat_slice(flat, i) for i in range(len(arena.names))])
+
+    save("parameters", gather(arena.P))
+    if "fc.bias" in arena.names:
+        save("gradient_fc_bias", arena.flat_slice(arena.G, arena.names.index("fc.bias")))
+    if reproducible_grads:
+        save("gradients", gather(arena.G))
+        buf = getattr(opt, "buf", None)
+        if buf is not None:
+            save("momentum", gather(buf))
+    bufs = dict(model.named_buffers())
+    for key in ("running_mean", "running_var"):
+        vals = [b.detach().reshape(-1).float() for n, b in bufs.items() if n.endswith(key)]
+        if vals:
+            save("bn_" + key, torch.cat(vals))
+    save("metrics", counters, torch.float64)
 
 
 def _self_launch(argv) -> int:
@@ -114,6 +175,13 @@ def main(argv=None):
                     help="fp8: e4m3 forward convs (block-scaled MFMA), bf16 backward; fp32: the reference's own "
                          "precision (imagenet.py:312 trains fp32): exact-f32 MFMA kernels with --kernels hip "
                          "(models/native_f32.py), PyTorch/MIOpen with --kernels torch")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them produced (parameters, "
+                         "BN running statistics, loss / top-k counters; with --deterministic 1 also gradients "
+                         "and momentum) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: two instrumented steps after the timed "
+                         "region for the bucket timeline (comm_overlap)")
     a = ap.parse_args(argv)
     f32_hip = a.dtype == "fp32" and a.kernels == "hip"
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "SLURM_PROCID" not in os.environ:
@@ -232,27 +300,61 @@ def main(argv=None):
             from imagent_amd.train.engine import GraphedStep
             one = GraphedStep(one, warmup=2, key_fn=lambda: opt.lr, two_stream=a.graph == 2)
 
-        def steps(n):
-            for u8, y in src.batches(n):
+        def steps(n, before_last=None):
+            for i, (u8, y) in enumerate(src.batches(n)):
+                if before_last is not None and i == n - 1:
+                    before_last()
                 one(u8, y)
+
+        # --dump-outputs: float atomics make two runs differ in the last bits, and 25 steps at lr 0.1 on random
+        # labels amplify that to unrelated weights. What the last timed step starts from is therefore put back to
+        # the seeded initial state, so that its outputs depend on the arguments and one step's rounding alone;
+        # its loss / top-k counters are kept apart from the running sums. The rewind runs inside the timed region
+        # (it has to precede the last step): copies of the masters and buffers, the shadow cast and a memset,
+        # ~0.3 ms of device time in the whole run. Restored: fp32 masters and their bf16 shadows, BN running
+        # statistics and shift (work.save), SGD / LARS momentum. Not restored: the fp8 scale history of
+        # --dtype fp8, whose dumps repeat less well for that reason
+        rewind = last_metrics = None
+        if a.dump_outputs:
+            state = [arena.P] + [b for b in model.buffers()]
+            state += [m.work.save for m in model.modules() if getattr(getattr(m, "work", None), "save", None)
+                      is not None]
+            state0 = [t.clone() for t in state]
+            seen = torch.zeros_like(metrics.buf)
+
+            def rewind():
+                torch._foreach_copy_(state, state0)
+                if native is not None:
+                    native.refresh_shadows(full=True)
+                if getattr(opt, "buf", None) is not None:
+                    opt.buf.zero_()
+                seen.copy_(metrics.buf)
+                metrics.buf.zero_()
 
         steps(a.warmup)
         ctx.barrier()
         sync()
         c0 = comm.collectives
         t0 = time.perf_counter()
-        steps(a.steps)
+        steps(a.steps, rewind)
         sync()
         ctx.barrier()
         t1 = time.perf_counter()
+        if rewind is not None and a.steps > 0:
+            last_metrics = metrics.buf.clone()
+            metrics.buf += seen
         coll_per_step = (comm.collectives - c0) / max(1, a.steps)
         T = max_over_ranks(t1 - t0)
         # the mean loss of the warm-up + timed steps only (read before the instrumented steps below)
         loss, _, _, _ = metrics.reduced(comm if ctx.world_size > 1 else None)
-        # after the timed region: two more steps with the bucket timeline recorded (parallel/ddp.py CommTimeline:
-        # exposed communication after the last backward kernel, per-bucket issue offsets, comm-stream busy time)
+        if a.dump_outputs and ctx.rank == 0:
+            _dump_outputs(a.dump_outputs, model, arena, opt, metrics.buf if last_metrics is None else last_metrics,
+                          reproducible_grads=bool(a.deterministic) or a.kernels == "torch")
+        # --full, after the timed region: two more steps with the bucket timeline recorded (parallel/ddp.py
+        # CommTimeline: exposed communication after the last backward kernel, per-bucket issue offsets,
+        # comm-stream busy time)
         overlap = None
-        if not a.graph:
+        if a.full and not a.graph:
             ddp.comm_timeline(True)
             steps(2)
             sync()
