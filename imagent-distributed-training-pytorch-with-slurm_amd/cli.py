@@ -41,6 +41,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "convs on the block-scaled MFMA with bf16 backward, fp32 = the reference's precision "
                         "(imagenet.py:312) on the own exact-f32 MFMA kernels (models/native_f32.py; every ResNet "
                         "depth, BatchNorm widths up to 2048 channels). --kernels torch: PyTorch ops (oracle)")
+    p.add_argument("--fp8-wgrad", action="store_true",
+                   help="with --dtype fp8 --kernels hip: weight gradients as e5m2 dY x e4m3 X on the 1-byte loop for "
+                        "the convs whose fp8 forward and fp8 dgrad already write both copies (ops.block.fp8_wgrad_ok; "
+                        "IMAGENT_FP8_WGRAD=1 does the same). Off by default")
     p.add_argument("--data", default="imagenet", choices=["imagenet", "records", "synthetic"],
                    help="imagenet: JPEG folders decoded by worker processes; records: train.imrec / val.imrec "
                         "(python -m imagent_amd.data.records) gathered by the native thread pool")

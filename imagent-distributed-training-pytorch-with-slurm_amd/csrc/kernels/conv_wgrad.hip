@@ -253,6 +253,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (BR == 32 ? 3 : 2) : 1) void wgr
 #include "conv_wgrad_v3.h"
 #include "conv_wgrad_stem.h"
 #include "conv_wgrad_halo.h"
+#include "conv_wgrad_fp8.h"
 
 namespace {
 
@@ -428,6 +429,55 @@ IMK_EXPORT int imk_stem_wgrad_bnx(const WgradArgs* args, const void* bnx, const 
     const WgradArgs& a = *args;
     if (!stem_wgrad_band_ok(a) || !bnx || !coef || a.OH % 2) return -106;
     return launch_stem_wgrad_band_bnx(a, (hipStream_t)stream, static_cast<const bf16_t*>(bnx), coef);
+}
+
+// the fp8 weight gradient (conv_wgrad_fp8.h): args->dY / args->X point at the e5m2 / e4m3 byte tensors, e_dy / e_x at
+// their device int32 exponents. variant: 0 / 2 64-row stages x 2, 1: 64 x 4, 3: 128 x 2, 4: 64 x 3 (A/B) -- fragments converted to
+// bf16 in registers; 5: 32 x 4; 11 / 12 / 13: the fp8 MFMA on the bytes (64 x 4 / 64 x 2 / 128 x 2; A/B only: its internal sum does
+// not hold the fp32 summation bound on full-range data). -106: not a
+// shape it covers (Ci % 128, Co % 128, stem, xbn) -- the caller runs the bf16 weight gradient
+IMK_EXPORT int imk_conv_wgrad_fp8(const WgradArgs* args, const int* e_dy, const int* e_x, int splits, int variant,
+                                  void* stream) {
+    const WgradArgs& a = *args;
+    if (!wgrad_fp8_ok(a) || !e_dy || !e_x) return -106;
+    if (a.M <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (variant) {
+        // (32 KB of LDS: four blocks per CU hide the conversions' latency; R50 shapes at 2048 img, summed per step:
+        // 64 x 2 9.70 ms, 64 x 3 10.20, 32 x 4 10.24, 128 x 2 11.34, 64 x 4 12.10; bf16 dispatch 11.87)
+        case 0:
+        case 2: return launch_wgrad_fp8<64, 2, 0>(a, e_dy, e_x, splits, st);
+        case 1: return launch_wgrad_fp8<64, 4, 0>(a, e_dy, e_x, splits, st);
+        case 3: return launch_wgrad_fp8<128, 2, 0>(a, e_dy, e_x, splits, st);
+        case 4: return launch_wgrad_fp8<64, 3, 0>(a, e_dy, e_x, splits, st);
+        case 11: return launch_wgrad_fp8<64, 4, 1>(a, e_dy, e_x, splits, st);
+        case 13: return launch_wgrad_fp8<128, 2, 1>(a, e_dy, e_x, splits, st);
+        case 5: return launch_wgrad_fp8<32, 4, 0>(a, e_dy, e_x, splits, st);
+        case 12: return launch_wgrad_fp8<64, 2, 1>(a, e_dy, e_x, splits, st);
+        default: return -106;
+    }
+}
+
+// one-wave probe of ds_read_b64_tr_b8 (conv_wgrad_fp8.h probe_tr8_kernel; host pointers): img[nbytes] -> LDS, lane l
+// reads at byte address addr[l], out[2 l], out[2 l + 1] are its registers. -106: an address out of range or unaligned
+IMK_EXPORT int imk_probe_ds_read_tr8(const uint8_t* img, int nbytes, const int* addr, uint32_t* out) {
+    if (!img || !addr || !out || nbytes < 8 || nbytes > 4096) return -106;
+    for (int l = 0; l < 64; ++l)
+        if (addr[l] < 0 || addr[l] % 8 || addr[l] + 8 > nbytes) return -106;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc(&d, 4096 + 64 * 4 + 128 * 4);
+    if (e != hipSuccess) return (int)e;
+    int* da = reinterpret_cast<int*>(d + 4096);
+    uint32_t* dout = reinterpret_cast<uint32_t*>(d + 4096 + 256);
+    e = hipMemcpy(d, img, nbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(da, addr, 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(probe_tr8_kernel, dim3(1), dim3(64), 0, nullptr, d, nbytes, da, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dout, 512, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return (int)e;
 }
 
 IMK_EXPORT int imk_wgrad_args_size() { return (int)sizeof(WgradArgs); }

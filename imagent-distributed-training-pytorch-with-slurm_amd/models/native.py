@@ -37,7 +37,7 @@ def stem_view(t: torch.Tensor, kw: int) -> torch.Tensor:
 
 class NativeState:
     def __init__(self, model: ResNet, device: torch.device, order: Optional[Sequence[int]] = None,
-                 bnb_fusion: bool = True, fp8: bool = False, wgrad_overlap: bool = True):
+                 bnb_fusion: bool = True, fp8: bool = False, wgrad_overlap: bool = True, fp8_wgrad: bool = False):
         self.device = torch.device(device)
         named = list(model.named_parameters())
         self.arena = ParamArena(named, self.device, order=order, with_shadow=True)
@@ -65,8 +65,11 @@ class NativeState:
         from ..ops import streams
         streams.set_wgrad_overlap(wgrad_overlap)
         self.fp8 = None
+        # --fp8-wgrad / IMAGENT_FP8_WGRAD=1 (with fp8 only; off by default): weight gradients of the convs of
+        # ops.block.fp8_wgrad_ok as e5m2 dY x e4m3 X; their e4m3 input copies then live until the backward pass
+        self.fp8_wgrad = bool(fp8) and (bool(fp8_wgrad) or os.environ.get("IMAGENT_FP8_WGRAD", "0") == "1")
         if fp8:
-            self.fp8 = Fp8State(self)
+            self.fp8 = Fp8State(self, wgrad=self.fp8_wgrad)
             for b in blocks:
                 b._q8 = self.fp8
             self._fp8_outputs()
@@ -81,6 +84,15 @@ class NativeState:
             return fp8_fwd_ok(b.conv1) or (b.downsample is not None and fp8_fwd_ok(b.downsample[0]))
         for k, b in enumerate(blocks):
             b._q8_out = k + 1 < len(blocks) and reads8(blocks[k + 1])
+            # does a BatchNorm-backward pass write the e5m2 copy of each conv's output gradient? Only the fused
+            # BatchNorm backward does, and the last block's last BatchNorm (+ downsample) is not finished by a next
+            # block's dgrad (ops.block.fp8_wgrad_ok)
+            last = k + 1 == len(blocks)
+            pairs = b.convs_bns()
+            for i, (c, _, _) in enumerate(pairs):
+                c._g8_copy = self.bnb_fusion and not (last and i + 1 == len(pairs))
+            if b.downsample is not None:
+                b.downsample[0]._g8_copy = self.bnb_fusion and not last
         self._q8_pool = bool(blocks) and reads8(blocks[0])
 
     # ------------------------------------------------------------ shadows
@@ -143,7 +155,7 @@ class NativeState:
         self._aff_dev = None  # the eval-affine table holds raw pointers into the old arena: rebuild it lazily
         self._bind_shadows()
         if self.fp8 is not None:
-            self.fp8 = Fp8State(self)
+            self.fp8 = Fp8State(self, wgrad=self.fp8_wgrad)
             for b in self.model.blocks():
                 b._q8 = self.fp8
             self._fp8_outputs()
@@ -228,10 +240,12 @@ class Fp8State:
     copies of the activations an fp8 forward conv reads and e5m2 copies of the gradients an fp8 dgrad reads
     (delayed per-tensor scales, written by the producing BN / pool pass). Which convs run fp8 is per shape
     (``ops.block.fp8_fwd_ok`` / ``fp8_dgrad_ok``: where the 1-byte v3 loop measured faster); weight
-    gradients and everything else stay bf16."""
+    gradients (unless ``wgrad``: ``ops.block.fp8_wgrad_ok``) and everything else stay bf16."""
 
-    def __init__(self, st: "NativeState", backward: bool = True):
+    def __init__(self, st: "NativeState", backward: bool = True, wgrad: bool = False):
         from ..ops.fp8 import E5M2_MAX, ActScales, WeightQuantizer
+        # weight gradients of ops.block.fp8_wgrad_ok convs on fp8 (--fp8-wgrad); needs the e5m2 gradient copies
+        self.wgrad = bool(wgrad) and backward
         m = st.model
         convs = [c for c in m.convs() if c is not m.conv1]
         self.wq = WeightQuantizer([c.weight for c in convs], st.device, transposed=backward)
@@ -249,6 +263,10 @@ class Fp8State:
         self.backward = backward
         self.grad = ActScales(len(bns), st.device, fmt_max=E5M2_MAX) if backward else None
         self.grad_ready = False
+        # the fp8 weight gradients wait for exponents that come from an observed backward pass: after_step() also
+        # runs when a model is bound (refresh_shadows), before any gradient amax exists
+        self._grad_seen = False
+        self.grad_scaled = False
         self.map = {}
         self.active = False
         self.wq.run()
@@ -260,12 +278,14 @@ class Fp8State:
         if self.grad is not None:
             self.grad.step()
             self.grad_ready = True
+            self.grad_scaled = self.grad_scaled or self._grad_seen
 
     def grad_out(self, like: torch.Tensor, bn):
         """(e5m2 buffer, exponent view, amax row) for a BN-backward output, or None."""
         if self.grad is None or like.shape[-1] % 16 or 256 % (like.shape[-1] // 8):
             return None
         i = self.slot[id(bn)]
+        self._grad_seen = True
         return (torch.empty(like.shape, dtype=torch.uint8, device=like.device), self.grad.exp[i:i + 1],
                 self.grad.amax[i])
 
@@ -293,9 +313,11 @@ class Fp8State:
 
 
 def bind_native(model: ResNet, device, order: Optional[Sequence[int]] = None,
-                bnb_fusion: bool = True, fp8: bool = False, wgrad_overlap: bool = True) -> NativeState:
+                bnb_fusion: bool = True, fp8: bool = False, wgrad_overlap: bool = True,
+                fp8_wgrad: bool = False) -> NativeState:
     model.to(device)
-    st = NativeState(model, device, order, bnb_fusion=bnb_fusion, fp8=fp8, wgrad_overlap=wgrad_overlap)
+    st = NativeState(model, device, order, bnb_fusion=bnb_fusion, fp8=fp8, wgrad_overlap=wgrad_overlap,
+                     fp8_wgrad=fp8_wgrad)
     model.native = st
     model.backend = "hip"
     st.refresh_shadows(full=True)

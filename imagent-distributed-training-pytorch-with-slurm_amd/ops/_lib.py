@@ -147,6 +147,8 @@ def _declare(name: str, lib) -> None:
             "imk_conv_igemm": [C.POINTER(IGemmArgs), i32, vp],
             "imk_conv_wgrad": [C.POINTER(WgradArgs), i32, vp],
             "imk_conv_wgrad_variant": [C.POINTER(WgradArgs), i32, i32, vp],
+            "imk_conv_wgrad_fp8": [C.POINTER(WgradArgs), vp, vp, i32, i32, vp],
+            "imk_probe_ds_read_tr8": [vp, i32, vp, vp],
             "imk_conv_launches": [],
             # fp32 path (f32.hip)
             "imk_conv_f32": [C.POINTER(IGemmArgs), vp],

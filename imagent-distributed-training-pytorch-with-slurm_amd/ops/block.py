@@ -141,6 +141,33 @@ def fp8_dgrad_ok(conv) -> bool:
     return co >= 512 or (co == 256 and ci <= 128)
 
 
+def fp8_wgrad_ok(conv) -> bool:
+    """Weight gradient on fp8 (``--fp8-wgrad``, e5m2 dY x e4m3 X on the 1-byte loop of conv_wgrad_fp8.h): only where
+    both 1-byte copies already exist -- the input's e4m3 copy of an fp8 forward and the output gradient's e5m2 copy
+    of an fp8 dgrad -- and the kernel covers the shape (whole 128-channel tiles); never the stem, never a conv whose
+    input is a BatchNorm applied on the operand path (``xbn``: those convs are not fp8 forwards). ``_g8_copy`` (set
+    when a model is bound, models/native.py): False where no pass writes the e5m2 copy -- the last block's last conv
+    and downsample conv, every conv without the fused BatchNorm backward."""
+    if getattr(conv, "stem", False) or not getattr(conv, "_g8_copy", True):
+        return False
+    return (fp8_fwd_ok(conv) and fp8_dgrad_ok(conv) and conv.in_channels % 128 == 0
+            and conv.out_channels % 128 == 0)
+
+
+def _keep8(q, conv, h8):
+    """The e4m3 input copy (bytes, exponent view) to keep for the conv's fp8 weight gradient, or None."""
+    if q is None or not q.wgrad or not q.grad_scaled or h8 is None or not fp8_wgrad_ok(conv):
+        return None
+    return (h8[0], h8[1])
+
+
+def _wg8(d8, x8):
+    """``conv_wgrad(fp8=)`` operands from the gradient's e5m2 copy and the kept e4m3 input copy, or None (bf16)."""
+    if d8 is None or x8 is None:
+        return None
+    return (d8[0], d8[1], x8[0], x8[1])
+
+
 def _fwd8(conv, h, h8, bn):
     """fp8 forward (``Fp8State``) when the input has an e4m3 copy and the shape is one fp8 wins, else bf16."""
     if h8 is None or conv.in_channels % 16 or not fp8_fwd_ok(conv):
@@ -167,11 +194,13 @@ def _gws(block, i):
     return w[i] if w is not None else None
 
 
-def _wgrad(conv, dA, h):
+def _wgrad(conv, dA, h, fp8=None):
     """``h`` is the conv's input, or (BN input, scale / shift) when the BN + ReLU before it is
-    applied on the operand path (``IMAGENT_BN_XFUSE``)."""
+    applied on the operand path (``IMAGENT_BN_XFUSE``). ``fp8``: :func:`_wg8` operands (``--fp8-wgrad``)."""
     if isinstance(h, tuple):
         conv_wgrad(conv, dA, h[0], xbn=h[1])
+    elif fp8 is not None:
+        conv_wgrad(conv, dA, h, fp8=fp8)
     else:
         conv_wgrad(conv, dA, h)
 
@@ -187,6 +216,10 @@ class BlockFn(torch.autograd.Function):
         saved = [x]
         h, h8 = x, x8
         ds = block.downsample
+        # --fp8-wgrad: the e4m3 input copies (conv index / "ds" -> (bytes, exponent view)) kept for the backward pass
+        wg8 = {}
+        if ds is not None and _keep8(q, ds[0], x8) is not None:
+            wg8["ds"] = _keep8(q, ds[0], x8)
         # the downsample conv depends only on x: with IMAGENT_DS_SIDE=1 it runs on the (idle in forward) side stream
         # beside the main chain's memory-bound BN passes (off by default, see _DS_SIDE)
         side = streams.side_stream(x.device) if (ds is not None and x.is_cuda and _DS_SIDE) else None
@@ -202,6 +235,8 @@ class BlockFn(torch.autograd.Function):
         for i, (conv, bn, _) in enumerate(pairs[:-1]):
             a = _fwd8(conv, h, h8, bn) if ss is None else \
                 igemm_fwd(h, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw, stats=bn.work, xbn=ss)
+            if ss is None and _keep8(q, conv, h8) is not None:
+                wg8[i] = _keep8(q, conv, h8)
             ss = None
             if not (gram and i + 1 == len(pairs) - 1) and _xfuse_ok(pairs[i + 1][0], a, q):
                 ss = xbn[i + 1] = bn_scale_shift(a, bn)
@@ -254,6 +289,8 @@ class BlockFn(torch.autograd.Function):
             a = igemm_fwd(h, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw, stats=bn.work, xbn=ss)
         else:
             a = _fwd8(conv, h, h8, bn)
+            if _keep8(q, conv, h8) is not None:
+                wg8[len(pairs) - 1] = _keep8(q, conv, h8)
         if not fused3:
             q8 = q.out_for(a, q.slot[id(bn)]) if need8 else None
             # the ReLU mask of the block output as bits, for the next block's conv1 dgrad epilogue (1/16
@@ -285,6 +322,7 @@ class BlockFn(torch.autograd.Function):
         block._bnb_done = False
         ctx.block = block
         ctx.xbn = xbn
+        ctx.wg8 = wg8 or None
         ctx.gram = gram
         ctx.h2sum = h2sum
         ctx.gram_P = gram_P  # W3 G from the fused forward (G in the block's workspace): not recomputed
@@ -314,6 +352,7 @@ class BlockFn(torch.autograd.Function):
         ds = block.downsample
         fuse = getattr(block, "_fuse_bnb", False)
         premasked = getattr(block, "_bnb_done", False)
+        wg8 = ctx.wg8 or {}  # kept e4m3 input copies (--fp8-wgrad)
         dA8 = None
         sparse = False
         if ds is not None:
@@ -338,7 +377,10 @@ class BlockFn(torch.autograd.Function):
             sparse = dconv.stride == 2 and dconv.kh == 1 and dconv.kw == 1 and dconv.padding == 0
             dX = igemm_dgrad(dAd, dconv.wt_bf16, (H, W), dconv.stride, dconv.padding, dconv.kh, dconv.kw,
                              fp8=_dg8(dAd8, dconv), sparse=sparse)
-            conv_wgrad(dconv, dAd, x)
+            if _wg8(dAd8, wg8.get("ds")) is not None:
+                conv_wgrad(dconv, dAd, x, fp8=_wg8(dAd8, wg8.get("ds")))
+            else:
+                conv_wgrad(dconv, dAd, x)
         elif premasked and ctx.gram and fuse:
             # dx3 kept as (g, A, B, c): no apply pass (ops/bn_gram.py); when the next block's dgrad ran without x3,
             # sum(g xhat3) comes from T = g^T h2 (formed here, reused by the weight gradient)
@@ -373,7 +415,7 @@ class BlockFn(torch.autograd.Function):
                                      conv.padding, conv.kh, conv.kw, bnb=fz, fp8=_dg8(dA8, conv))
                 if h_in is None:  # xfuse: the weight gradient applies the BN on its operand staging
                     h_in = (acts[i - 1], xbn[i])
-                dA_w = dA
+                dA_w, dA8_w = dA, dA8  # (dA8 is reassigned by the BN pass below: the copy that belongs to dA_w)
                 if fz is not None:
                     g8a = q.grad_out(acts[i - 1], bn_prev) if (q is not None and fp8_dgrad_ok(pairs[i - 1][0])) else None
                     dA, _ = bn_apply_backward(dH, acts[i - 1], None, bn_prev, None, 0, g8=(g8a, None))
@@ -384,7 +426,7 @@ class BlockFn(torch.autograd.Function):
                 if not isinstance(dA_w, GramBN):
                     # issued after the BN-backward pass: the side-stream weight gradient then runs
                     # beside the next (compute-bound) dgrad instead of the memory-bound BN pass
-                    _wgrad(conv, dA_w, h_in)
+                    _wgrad(conv, dA_w, h_in, fp8=_wg8(dA8_w, wg8.get(i)))
             else:
                 prev = getattr(block, "_prev_block", None)
                 fz = None
@@ -402,7 +444,11 @@ class BlockFn(torch.autograd.Function):
                 igemm_dgrad(dA, conv.wt_bf16, (H, W), conv.stride, conv.padding, conv.kh, conv.kw, out=dX,
                             accumulate=True, bnb=fz, fp8=_dg8(dA8, conv), old_sub2=(ds is not None and sparse))
                 # issued by the previous block's backward after its BN pass
-                streams.defer(lambda c=conv, g=dA, h=h_in: conv_wgrad(c, g, h))
+                f8 = _wg8(dA8, wg8.get(i))  # (the closure holds the byte tensors until the launch)
+                if f8 is not None:
+                    streams.defer(lambda c=conv, g=dA, h=h_in, f=f8: conv_wgrad(c, g, h, fp8=f))
+                else:
+                    streams.defer(lambda c=conv, g=dA, h=h_in: conv_wgrad(c, g, h))
                 if fz is not None:
                     prev._bnb_done = True
                     prev._bnb_nox = nox

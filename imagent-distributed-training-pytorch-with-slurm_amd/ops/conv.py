@@ -348,6 +348,30 @@ def igemm_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, stride: int
     _wgrad_call(a, splits, _lib.stream_ptr(), "conv wgrad")
 
 
+def igemm_wgrad_fp8(dy8: torch.Tensor, x8: torch.Tensor, dw: torch.Tensor, e_dy: torch.Tensor, e_x: torch.Tensor,
+                    stride: int, pad: int, KH: int, KW: int, splits: int = 0, variant: int = 0) -> bool:
+    """dw[Co, KH*KW*Ci] (fp32) += 2^(e_dy + e_x) * wgrad(dy8[N,OH,OW,Co] e5m2 bytes, x8[N,H,W,Ci] e4m3 bytes) on the
+    1-byte weight-gradient loop (conv_wgrad_fp8.h); ``e_dy`` / ``e_x``: device int32 scalars (:class:`ops.fp8.ActScales`).
+    False (nothing launched) when the kernel does not cover the shape (Ci % 128, Co % 128): the caller runs the bf16
+    weight gradient. ``variant`` (A/B): the stage shapes of ``imk_conv_wgrad_fp8``."""
+    assert dy8.dtype == torch.uint8 and x8.dtype == torch.uint8, (dy8.dtype, x8.dtype)
+    assert dy8.is_contiguous() and x8.is_contiguous() and dw.dtype == torch.float32
+    assert e_dy.dtype == torch.int32 and e_x.dtype == torch.int32
+    a = _wgrad_args(dy8, x8, dw, stride, pad, KH, KW, False, None)
+    assert dw.numel() == a.Co * KH * KW * a.Ci, (dw.shape, a.Co, KH, KW, a.Ci)
+    k = _lib.kernels()
+    st = _lib.stream_ptr()
+    n0 = k.imk_conv_launches() if _LOG_PATH is not None else 0
+    r = k.imk_conv_wgrad_fp8(C.byref(a), e_dy.data_ptr(), e_x.data_ptr(), splits, variant, st)
+    if r == -106:
+        return False
+    _lib.check(r, "conv wgrad fp8")
+    if _LOG_PATH is not None:
+        _log(dict(op="conv wgrad fp8", N=a.N, H=a.H, W=a.W, C=a.Ci, Co=a.Co, OH=a.OH, OW=a.OW, M=a.M, KH=a.KH,
+                  KW=a.KW, stride=a.stride, stem=False, xbn=False), k.imk_conv_launches() - n0, st)
+    return True
+
+
 def stem_wgrad_bnx(g: torch.Tensor, x: torch.Tensor, gp: torch.Tensor, bnx: torch.Tensor, coef: torch.Tensor,
                    stride: int, pad: int, KH: int, KW: int) -> bool:
     """The stem's weight gradient with its BatchNorm's backward apply fused into the operand staging
@@ -419,27 +443,36 @@ class ConvFn(torch.autograd.Function):
         return dx, None, None, None
 
 
-def conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tensor] = None) -> None:
+def conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tensor] = None, fp8=None) -> None:
     """Accumulate a Conv2d module's weight gradient into its arena slot and
     signal the bucketed reducer (on the wgrad side stream when enabled,
     ``ops/streams.py``). ``xbn``: x is a BatchNorm's INPUT whose apply + ReLU
-    the kernel does on its operand staging (:func:`igemm_wgrad`)."""
+    the kernel does on its operand staging (:func:`igemm_wgrad`).
+    ``fp8 = (dy8, e_dy, x8, e_x)``: the e5m2 copy of dy and the e4m3 copy of x with their device exponents -- the
+    weight gradient reads those (:func:`igemm_wgrad_fp8`) where the 1-byte loop covers the shape, else dy and x."""
     side = streams.side_stream(dy.device) if dy.is_cuda else None
     if side is None:
-        _conv_wgrad(mod, dy, x, xbn)
+        _conv_wgrad(mod, dy, x, xbn, fp8)
         return
     streams.wait(side, torch.cuda.current_stream(dy.device))
     with torch.cuda.stream(side):
-        _conv_wgrad(mod, dy, x, xbn)
+        _conv_wgrad(mod, dy, x, xbn, fp8)
     if xbn is not None:
         streams.protect(dy, x, xbn)
     else:
         streams.protect(dy, x)
+    if fp8 is not None:
+        streams.protect(*fp8)
     streams.ensure_join_after_backward()
 
 
-def _conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tensor] = None) -> None:
+def _conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tensor] = None, fp8=None) -> None:
     gp = getattr(mod, "grad_pad", None)
+    if fp8 is not None and gp is None and xbn is None:
+        dy8, e_dy, x8, e_x = fp8
+        if igemm_wgrad_fp8(dy8, x8, mod.weight.grad, e_dy, e_x, mod.stride, mod.padding, mod.kh, mod.kw):
+            notify_ready(mod.weight)
+            return
     if gp is not None:  # stem: [Co][KH][32] row-segment layout (zero between steps) -> master [Co][KH][KW][Ci]
         igemm_wgrad(dy, x, gp, mod.stride, mod.padding, mod.kh, mod.kw, stem=True)
         g = mod.weight.grad  # the arena's [Co][Ci][KH][KW] view of [Co][KH][KW][Ci] storage

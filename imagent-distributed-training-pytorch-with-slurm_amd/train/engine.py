@@ -214,6 +214,9 @@ def _master_print(is_master, *a, **kw):
 class Trainer:
     def __init__(self, args):
         self.args = a = args
+        if getattr(a, "fp8_wgrad", False) and (a.dtype != "fp8" or a.kernels == "torch"):
+            raise SystemExit("--fp8-wgrad needs --dtype fp8 --kernels hip (the fp8 weight gradient reads the 1-byte "
+                             f"copies of the fp8 forward and dgrad): got --dtype {a.dtype} --kernels {a.kernels}")
         torch.manual_seed(a.seed)  # imagenet.py:215
         self.topo = launcher.discover(a.launcher)
         if not a.quiet_banner:
@@ -289,6 +292,8 @@ class Trainer:
         self.dtype = {"bf16": torch.bfloat16, "fp8": torch.bfloat16, "fp32": torch.float32}[a.dtype]
         if a.dtype == "fp8" and self.kernels != "hip":
             raise SystemExit("--dtype fp8 needs the HIP kernels (--kernels hip on a MI355X)")
+        if getattr(a, "fp8_wgrad", False) and self.kernels != "hip":
+            raise SystemExit("--fp8-wgrad needs the HIP kernels (--kernels hip on a MI355X)")
         rs = getattr(a, "record_resize", False)
         self.transform_train = InputTransform(self.kernels, size, cpad=resnet.ResNet.STEM_CPAD,
                                               flip=a.flip, dtype=torch.float32, resize=rs)
@@ -335,8 +340,14 @@ class Trainer:
                 set_deterministic(True)
             # IMAGENT_WGRAD_OVERLAP=0: weight gradients on the main stream (A/B and diagnostics)
             self.native = bind_native(model, self.device, order, fp8=a.dtype == "fp8",
-                                      wgrad_overlap=os.environ.get("IMAGENT_WGRAD_OVERLAP", "1") != "0")
+                                      wgrad_overlap=os.environ.get("IMAGENT_WGRAD_OVERLAP", "1") != "0",
+                                      fp8_wgrad=getattr(a, "fp8_wgrad", False))
             arena = self.native.arena
+            if self.native.fp8 is not None and self.native.fp8.wgrad:
+                from ..ops.block import fp8_wgrad_ok
+                n8 = sum(fp8_wgrad_ok(c) for c in model.convs())
+                _master_print(self.is_master, f"fp8 weight gradients: {n8} of {len(model.convs())} convs "
+                                              "(e5m2 dY x e4m3 X, from the second step on)")
         else:
             model.to(self.device)
             arena = ParamArena(list(model.named_parameters()), self.device, order=order)
