@@ -6,7 +6,8 @@
   (``csrc/comm``), linked against the ``librccl.so`` bundled with torch (the
   same library c10d's ProcessGroupNCCL uses).
 * ``_native/libimagent_runtime.so`` - host runtime (bucket planner / ready
-  tracker, ``csrc/runtime``), plain C++.
+  tracker, record loader, the weight-gradient launchers' split planner,
+  ``csrc/runtime``), plain C++.
 
 All three expose a C ABI and are loaded with ctypes (``ops/_lib.py``), so they
 do not depend on the torch C++ ABI. A library is rebuilt when the SHA-256 of its
@@ -149,15 +150,16 @@ def build_comm(force: bool = False) -> str:
 
 def build_runtime(force: bool = False) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
+    hdrs = [os.path.join(CSRC, "kernels", "conv_wgrad_plan.h")]  # (wgrad_plan.cpp: the launchers' split planner)
     out = os.path.join(OUT, "libimagent_runtime.so")
     cxx = shutil.which("g++") or "c++"
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", out] + srcs
     key = ["runtime"] + cmd  # the whole command line: a flag change rebuilds
-    if not force and not _stale(srcs, out, key):
+    if not force and not _stale(srcs + hdrs, out, key):
         return out
     os.makedirs(OUT, exist_ok=True)
     _run(cmd)
-    _stamp(srcs, out, key)
+    _stamp(srcs + hdrs, out, key)
     return out
 
 

@@ -65,6 +65,41 @@ __device__ __forceinline__ void buf_st16(__amdgpu_buffer_rsrc_t r, uint32_t off,
     __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
 }
 
+// a descriptor over `bytes` bytes from p (at most 2^31 - 1): offsets at or past the end read zeros
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc_n(const void* p, size_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)min(bytes, (size_t)0x7FFFFFFF),
+                                             0x00020000);
+}
+// LDS-DMA fill: lane l's 16 bytes at offset `off` land at lds + 16 l (lds wave-uniform), zeros when out of range
+__device__ __forceinline__ void buf_dma16(__amdgpu_buffer_rsrc_t r, char* lds, uint32_t off) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (LDS_PTR(void))lds, 16, off, 0, 0, 0);
+}
+
+// one lane's 8 k-values of a 16x16x32 bf16 MFMA fragment from a row-major ([k][channel]) LDS image: two
+// transposing reads (ds_read_b64_tr_b16, cdna_hip_programming.md T10), a / b this lane's row addresses
+__device__ __forceinline__ bf16x8 tr16_frag(const char* a, const char* b) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))a);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))b);
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// the same from a base and two offsets: each address is formed just before its read. In the fully unrolled k-loops of
+// wgrad_v3_kernel the two-pointer form (both addresses formed first) moved reads against MFMAs in three instantiations
+// and measured +1.0 .. +1.2 % per step on two of them (profiles/wgrad_refactor.md)
+__device__ __forceinline__ bf16x8 tr16_frag(const char* base, int oa, int ob) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(base + oa));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(base + ob));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// counted waits for hand-ordered LDS-DMA rings: at most N vector-memory operations still in flight (expcnt and
+// lgkmcnt left free), and LDS / scalar-memory operations only (vmcnt left free)
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+    static_assert(N >= 0 && N < 64, "vmcnt range");
+    __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4) | (0xF << 8));
+}
+__device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4)); }
+
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
     if (nwg <= 8) return orig;
     const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;

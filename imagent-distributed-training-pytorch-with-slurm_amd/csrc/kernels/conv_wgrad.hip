@@ -21,32 +21,16 @@
 // tiles are added with no-return fp32 atomics in 64-B row segments (the
 // chip-wide atomic rate, ~1.3 TB/s, is far above what these tiles need).
 // Index math for the gather uses host-computed magic-number division.
+//
+// This translation unit: the register-staged kernel (here), the LDS-DMA loops (conv_wgrad_v3.h, conv_wgrad_fp8.h),
+// the halo-tiled 3x3 (conv_wgrad_halo.h) and the stem band kernel (conv_wgrad_stem.h), then the dispatch. They share
+// WgradArgs, the gather, the block decode and the atomic epilogue (conv_wgrad_shared.h), the LDS-DMA / transposed-read
+// / counted-wait helpers of common.h, and one host split-K planner (conv_wgrad_plan.h).
 
-#include <cstdlib>
-
-#include "common.h"
-
-struct WgradArgs {
-    const bf16_t* dY;  // [M][Co]  (NHWC of the conv output)
-    const bf16_t* X;   // NHWC [N][H][W][Ci]
-    float* dW;         // [Co][KH*KW*Ci] fp32, accumulated (+=)
-    int N, H, W, Ci, Co;
-    int OH, OW, M;
-    int KH, KW, stride, pad;
-    int m_per_split;   // multiple of BR
-    uint32_t mg_ohw, sh_ohw, mg_ow, sh_ow;  // magic division by OH*OW and OW
-    int stem;          // bit 0: C == 4 row-segment gather, dW is [Co][KH][32]
-    // the X operand is relu(X * xbn[c] + xbn[Ci + c]) (BatchNorm apply + ReLU of the conv's input,
-    // never materialised: ops/block.py); out-of-image taps stay 0
-    const float* xbn;
-};
+#include "conv_wgrad_plan.h"
+#include "conv_wgrad_shared.h"
 
 namespace {
-
-
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, uint32_t mg, uint32_t sh) {
-    return (uint32_t)(((uint64_t)__umulhi(n, mg) + n) >> sh);
-}
 
 // NW waves per block: 4 (two blocks per CU) or 8 (one 256x256 block per CU:
 // half the operand bytes per MFMA FLOP of a 128x128 tile)
@@ -133,22 +117,19 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (BR == 32 ? 3 : 2) : 1) void wgr
             u32x4 v = {0, 0, 0, 0};
             if (XB) xok[i] = false;
             if (m < mend && xk_ok) {
-                const uint32_t img = fdiv((uint32_t)m, a.mg_ohw, a.sh_ohw);
-                const uint32_t rem = (uint32_t)m - img * (uint32_t)(a.OH * a.OW);
-                const uint32_t oh = fdiv(rem, a.mg_ow, a.sh_ow);
-                const uint32_t ow = rem - oh * (uint32_t)a.OW;
-                const int ih = (int)oh * a.stride + xdh, iw = (int)ow * a.stride + xdw;
-                if (STEM) {
-                    if ((unsigned)ih < (unsigned)a.H) {
-                        const bf16_t* p = a.X + (((long)img * a.H + ih) * a.W + iw) * 4;
+                const WgradPix px = wgrad_pix((uint32_t)m, (uint32_t)(a.OH * a.OW), (uint32_t)a.OW, a.mg_ohw, a.sh_ohw,
+                                              a.mg_ow, a.sh_ow, a.stride, xdh, xdw);
+                if (STEM) {  // two taps (4 channels each) of the row segment, each with its own column test
+                    if ((unsigned)px.ih < (unsigned)a.H) {
+                        const bf16_t* p = a.X + wgrad_pix_row<long>(px, 0, a.H, a.W) * 4;
                         u32x2 lo = {0, 0}, hi = {0, 0};
-                        if (xkw0 < a.KW && (unsigned)iw < (unsigned)a.W) lo = *reinterpret_cast<const u32x2*>(p);
-                        if (xkw0 + 1 < a.KW && (unsigned)(iw + 1) < (unsigned)a.W)
+                        if (xkw0 < a.KW && (unsigned)px.iw < (unsigned)a.W) lo = *reinterpret_cast<const u32x2*>(p);
+                        if (xkw0 + 1 < a.KW && (unsigned)(px.iw + 1) < (unsigned)a.W)
                             hi = *reinterpret_cast<const u32x2*>(p + 4);
                         v = u32x4{lo[0], lo[1], hi[0], hi[1]};
                     }
-                } else if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-                    v = *reinterpret_cast<const u32x4*>(a.X + (((size_t)img * a.H + ih) * a.W + iw) * a.Ci + xci);
+                } else if (wgrad_pix_in(px, a.H, a.W)) {
+                    v = *reinterpret_cast<const u32x4*>(a.X + wgrad_pix_row<size_t>(px, 0, a.H, a.W) * a.Ci + xci);
                     if (XB) xok[i] = true;
                 }
             }
@@ -206,21 +187,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? (BR == 32 ? 3 : 2) : 1) void wgr
             for (int i = 0; i < FN; ++i) {
                 const int col = wco * TCO + i * 16 + 4 * p;
                 const char* base = d + (ks * 32) * PCO + col * 2;
-                s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (LDS_PTR(s16x4))(base + row_a * PCO));
-                s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (LDS_PTR(s16x4))(base + row_b * PCO));
-                fd[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                fd[i] = tr16_frag(base + row_a * PCO, base + row_b * PCO);
             }
 #pragma unroll
             for (int j = 0; j < FM; ++j) {
                 const int col = wkc * TKC + j * 16 + 4 * p;
                 const char* base = x + (ks * 32) * PKC + col * 2;
-                s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (LDS_PTR(s16x4))(base + row_a * PKC));
-                s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (LDS_PTR(s16x4))(base + row_b * PKC));
-                fx[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                fx[j] = tr16_frag(base + row_a * PKC, base + row_b * PKC);
             }
 #pragma unroll
             for (int i = 0; i < FN; ++i)
@@ -261,23 +234,17 @@ template <int BCO, int BKC, int WCO, bool STEM, int NW = 4, int BR = 64, bool XB
 int launch1(WgradArgs a, int splits, hipStream_t st) {
     const int K = STEM ? a.KH * 32 : a.KH * a.KW * a.Ci;
     const int ntiles = ((a.Co + BCO - 1) / BCO) * ((K + BKC - 1) / BKC);
-    if (splits <= 0) {
-        // ~3 blocks per CU over 256 CUs (4-wave blocks, 2 resident per CU) or
-        // ~2 (8-wave blocks, 1 resident), at least 4 stages per block
-        // measured (conv_bench, R50 at 1024 img): the stem and the <= 128-channel 3x3 convs
-        // (few tiles, latency-bound staging) gain from 4-5 blocks per CU (stem 1108 -> 944 us,
-        // 64@56 3x3 630 -> 577, 128@28 3x3 502 -> 461); 1x1 convs lose (more split-K atomics)
-        int target = NW == 4 ? 768 : 512;
-        if (NW == 4 && STEM) target = 1280;
-        else if (NW == 4 && a.KH * a.KW > 1 && a.Ci <= 128) target = 1024;
-        const int want = (target + ntiles - 1) / ntiles;
-        const int maxs = (a.M + 4 * BR - 1) / (4 * BR);
-        splits = max(1, min(want, maxs));
-    }
-    int mps = (a.M + splits - 1) / splits;
-    mps = (mps + BR - 1) / BR * BR;
-    splits = (a.M + mps - 1) / mps;
-    a.m_per_split = mps;
+    // ~3 blocks per CU over 256 CUs (4-wave blocks, 2 resident per CU) or
+    // ~2 (8-wave blocks, 1 resident), at least 4 stages per block
+    // measured (conv_bench, R50 at 1024 img): the stem and the <= 128-channel 3x3 convs
+    // (few tiles, latency-bound staging) gain from 4-5 blocks per CU (stem 1108 -> 944 us,
+    // 64@56 3x3 630 -> 577, 128@28 3x3 502 -> 461); 1x1 convs lose (more split-K atomics)
+    int target = NW == 4 ? 768 : 512;
+    if (NW == 4 && STEM) target = 1280;
+    else if (NW == 4 && a.KH * a.KW > 1 && a.Ci <= 128) target = 1024;
+    const WgradPlan pl = wgrad_plan(a.M, ntiles, BR, target, splits);  // (64-bit pointers: no byte limits)
+    splits = pl.splits;
+    a.m_per_split = pl.m_per_split;
     const size_t lds = (size_t)2 * BR * ((BCO * 2 + 32) + (BKC * 2 + 32));
     hipLaunchKernelGGL((wgrad_kernel<BCO, BKC, WCO, STEM, NW, BR, XB>), dim3(ntiles * splits), dim3(NW * 64), lds,
                        st, a);
@@ -299,6 +266,30 @@ int launch(WgradArgs a, int splits, hipStream_t st) {
     }
     return br32 ? launch1<BCO, BKC, WCO, STEM, 4, 32>(a, splits, st)
                 : launch1<BCO, BKC, WCO, STEM, 4, 64>(a, splits, st);
+}
+
+// the register-staged kernel's tile by output channels
+int launch_staged(const WgradArgs& a, int splits, hipStream_t st) {
+    return a.Co <= 64 ? launch<64, 128, 1, false>(a, splits, st) : launch<128, 128, 2, false>(a, splits, st);
+}
+
+// the LDS-DMA loop (conv_wgrad_v3.h, the caller checks wgrad_v3_ok) by stage-shape id -- the values of IMAGENT_WGRAD_V3
+// and of imk_conv_wgrad_variant: 1: 64-row stages x 2, 2: 64 x 3, 3: 32 x 4, 4: 128 x 2, 6: 64 x 2 on the 256 x 256
+// tile (-106 where that does not cover the shape); -106: no such id
+int launch_v3_shape(int id, const WgradArgs& a, int splits, hipStream_t st) {
+    switch (id) {
+        case 1: return launch_wgrad_v3<64, 2>(a, splits, st);
+        case 2: return launch_wgrad_v3<64, 3>(a, splits, st);
+        case 3: return launch_wgrad_v3<32, 4>(a, splits, st);
+        case 4: return launch_wgrad_v3<128, 2>(a, splits, st);
+        // 256 x 256 tile on 16 waves, one block per CU (64-row stages x 2): isolated 1x1 wgrads at 2048 img 12-26 %
+        // faster on the strided / 28x28 / 1024 -> 512 shapes, 2-4 % on the rest (32-row x 4 stages and the 8-wave
+        // 128 x 256 / 256 x 128 tiles measured slower than the 128 x 128 tile); in-step neutral as the 1x1 default
+        // (16,527 / 16,572 vs 16,522 / 16,542 img/s: its 128-KB blocks do not co-reside with the main stream's), so
+        // dispatched for large steps only, below (scripts/wgrad_ab.py --set 1x1, README round 5)
+        case 6: return wgrad_v3w_ok<4, 4>(a) ? launch_wgrad_v3<64, 2, 4, 4>(a, splits, st) : -106;
+        default: return -106;
+    }
 }
 
 }  // namespace
@@ -324,14 +315,8 @@ IMK_EXPORT int imk_conv_wgrad(const WgradArgs* args, int splits, void* stream) {
     // is 4-15 % ahead on those 3x3 shapes (round 5, below); in-step on the side stream the LDS-DMA loop wins: 4096 img
     // 17,276 / 17,257 -> 17,354 / 17,330 img/s, 256 img 13,535 -> 13,567 (round 6, scripts/runs/wgv3_ab.sh, every
     // production shape's numerics in tests/test_conv_shapes_gpu.py)
-    static const int v3 = [] {
-        const char* e = getenv("IMAGENT_WGRAD_V3");
-        return e ? atoi(e) : 6;
-    }();
-    static const int halo_mode = [] {  // IMAGENT_WGRAD_HALO, see the halo-kernel branch below
-        const char* e = getenv("IMAGENT_WGRAD_HALO");
-        return e ? atoi(e) : 2;
-    }();
+    static const long v3 = env_int("IMAGENT_WGRAD_V3", 6);
+    static const long halo_mode = env_int("IMAGENT_WGRAD_HALO", 2);  // see the halo-kernel branch below
     // 6 also takes the 256 x 256 tile (16 waves, one block per CU, its own split count) when the step is large:
     // at least IMAGENT_WGRAD_WIDE_MIN_IMAGES images per GPU (default 2048); 7 (A/B): wherever it covers the shape.
     // In-step, one box each (scripts/runs/wgv7_ab.sh, wide_ab.sh): everywhere at 4096 img 17,419 / 17,392 ->
@@ -339,26 +324,16 @@ IMK_EXPORT int imk_conv_wgrad(const WgradArgs* args, int splits, void* stream) {
     // (>= 200,704 pixels: layers 1-2 at 256 img) 13,435 / 13,448 -> 13,386 / 13,390 -- the 128-KB blocks keep the
     // small main-stream kernels of a small step from co-residing (round 5's note above imk_conv_wgrad_variant), so
     // the bound is on the step size; at 2048 img round 5 measured the tile neutral in-step
-    static const long wide_min = [] {
-        const char* e = getenv("IMAGENT_WGRAD_WIDE_MIN_IMAGES");
-        return e ? atol(e) : 2048L;
-    }();
+    static const long wide_min = env_int("IMAGENT_WGRAD_WIDE_MIN_IMAGES", 2048);
     const bool v3_rest = (v3 == 6 || v3 == 7) && !(halo_mode && wgrad_halo_ok(a, halo_mode >= 2, true));
     if (v3 && wgrad_v3_ok(a) && (v3 == 5 || v3_rest || (a.KH == 1 && a.KW == 1))) {
         if ((v3 == 7 || (v3 == 6 && (long)a.N >= wide_min)) && wgrad_v3w_ok<4, 4>(a))
-            return launch_wgrad_v3<64, 2, 4, 4>(a, 0, st);
-        switch (v3) {
-            case 2: return launch_wgrad_v3<64, 3>(a, splits, st);
-            case 3: return launch_wgrad_v3<32, 4>(a, splits, st);
-            case 4: return launch_wgrad_v3<128, 2>(a, splits, st);
-            default: return launch_wgrad_v3<64, 2>(a, splits, st);
-        }
+            return launch_v3_shape(6, a, 0, st);
+        return launch_v3_shape(v3 >= 2 && v3 <= 4 ? (int)v3 : 1, a, splits, st);
     }
     // 3x3 stride-1 with 64-channel slices: the halo-tiled kernel (conv_wgrad_halo.h); IMAGENT_WGRAD_HALO=0 off,
     // 1 only 64 -> 64, 2 (default) every shape it covers
-    const int halo = halo_mode;  // (read once above)
-    if (halo && wgrad_halo_ok(a, halo >= 2, true)) return launch_wgrad_halo(a, st);
-    if (a.Co <= 64) return launch<64, 128, 1, false>(a, splits, st);
+    if (halo_mode && wgrad_halo_ok(a, halo_mode >= 2, true)) return launch_wgrad_halo(a, st);
     // (an LDS-DMA ring variant with a 2*(row&7)-swizzled 256-B-row image measured
     // 2 % slower than this register-staged loop on every R50 shape: not kept)
     // (launch<256, 256, 2, false, 8> -- one 8-wave block per CU -- measured 23 %
@@ -366,7 +341,7 @@ IMK_EXPORT int imk_conv_wgrad(const WgradArgs* args, int splits, void* stream) {
     // (round 5, 2048 img, 3x3 stride 2 / 7x7: the LDS-DMA loop waits on its fills -- SQ_WAIT_ANY 44 % of wave
     // cycles vs 22 % here, scripts/pmc_wgrad.sh; deeper rings cost blocks per CU and run slower still, 32-row
     // stages x 2 at four blocks per CU come within 4 % on 512 @7 and stay 5-15 % behind on the stride-2 shapes)
-    return launch<128, 128, 2, false>(a, splits, st);
+    return launch_staged(a, splits, st);
 }
 
 // explicit kernel choice (tests, A/B): -1 the register-staged kernel, -2 the stem's register-staged kernel, 1..4
@@ -383,23 +358,10 @@ IMK_EXPORT int imk_conv_wgrad_variant(const WgradArgs* args, int splits, int var
     }
     if (variant < 0) {
         if (a.stem || a.xbn || a.Ci % 8 || a.Co % 8) return -106;
-        return a.Co <= 64 ? launch<64, 128, 1, false>(a, splits, st) : launch<128, 128, 2, false>(a, splits, st);
+        return launch_staged(a, splits, st);
     }
     if (variant == 9) return wgrad_halo_ok(a) ? launch_wgrad_halo(a, st) : -106;
-    if (!wgrad_v3_ok(a)) return -106;
-    switch (variant) {
-        case 1: return launch_wgrad_v3<64, 2>(a, splits, st);
-        case 2: return launch_wgrad_v3<64, 3>(a, splits, st);
-        case 3: return launch_wgrad_v3<32, 4>(a, splits, st);
-        case 4: return launch_wgrad_v3<128, 2>(a, splits, st);
-        // 256 x 256 tile on 16 waves, one block per CU (64-row stages x 2): isolated 1x1 wgrads at 2048 img 12-26 %
-        // faster on the strided / 28x28 / 1024 -> 512 shapes, 2-4 % on the rest (32-row x 4 stages and the 8-wave
-        // 128 x 256 / 256 x 128 tiles measured slower than the 128 x 128 tile); in-step neutral as the 1x1 default
-        // (16,527 / 16,572 vs 16,522 / 16,542 img/s: its 128-KB blocks do not co-reside with the main stream's), so
-        // not dispatched (scripts/wgrad_ab.py --set 1x1, README round 5)
-        case 6: return wgrad_v3w_ok<4, 4>(a) ? launch_wgrad_v3<64, 2, 4, 4>(a, splits, st) : -106;
-        default: return -106;
-    }
+    return wgrad_v3_ok(a) ? launch_v3_shape(variant, a, splits, st) : -106;
 }
 
 // G += h2^T h2 for an [M][p] bf16 h2 (the Gram-form bottleneck's Gram matrix, ops/bn_gram.py), p = 64 / 128, G fp32

@@ -4,10 +4,11 @@
 // copy of the conv's input), e_dy / e_x their device-resident power-of-two exponents (ops/fp8.py ActScales), dW fp32
 // in the gradient arena. Ci % 128 == 0 and Co % 128 == 0; anything else is the bf16 loop's.
 //
-// Carried over from wgrad_v3_kernel: LDS-DMA fills through buffer descriptors based per split (32-bit offsets hold
-// for tensors over 2^31 bytes), one filter tap per 128-channel k tile with out-of-image taps as out-of-range offsets
-// (zeros), an NS-deep ring with counted vmcnt and one s_barrier per stage, split-K over m with fp32 atomics, the
-// XCD-aware block order, and the launcher's m_per_split rules. What differs for 1-byte operands:
+// Shared with wgrad_v3_kernel (conv_wgrad_shared.h, conv_wgrad_plan.h): the per-block work decode with its per-split
+// buffer descriptors (32-bit offsets hold for tensors over 2^31 bytes) and XCD-aware block order, the pixel gather of
+// one filter tap per 128-channel k tile (out-of-image taps as out-of-range offsets: zeros), the fp32-atomic epilogue
+// and the launcher's split-K plan; the same NS-deep ring with counted vmcnt and one s_barrier per stage. What this
+// file holds is what differs for 1-byte operands:
 //  * LDS image: plain 128-B rows (one pixel x 128 channels), 16-B chunk ch of row r at slot ch ^ ((r >> 1) & 7).
 //    A 1-KB DMA instruction fills 8 whole rows; the XOR is applied on the source side (lane -> source chunk).
 //  * fragments by the 8-bit transposing LDS read ds_read_b64_tr_b8: a 16-lane group reads a block of 8 rows
@@ -25,7 +26,8 @@
 
 #pragma once
 
-#include "common.h"
+#include "conv_wgrad_plan.h"
+#include "conv_wgrad_shared.h"
 
 namespace {
 
@@ -78,41 +80,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_fp8_kernel(const WgradArgs a, co
     constexpr int PP = (BR / 8) / NW;      // 1-KB pieces (8 rows) per wave, operand and stage
     static_assert(BR % 32 == 0 && PP >= 1 && PP * NW * 8 == BR, "piece split");
     constexpr int LPS = 2 * PP;            // DMA instructions per wave per stage
-    static_assert((NS - 2) * LPS < 64, "vmcnt range");
     constexpr int NKS = BR / 32;           // MFMA k-steps per stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sD = smem;
     char* sX = smem + NS * SI;
-    const uint8_t* gD = reinterpret_cast<const uint8_t*>(a.dY);
-    const uint8_t* gX = reinterpret_cast<const uint8_t*>(a.X);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wco = wid & 1, wkc = wid >> 1;
-    const int K = a.KH * a.KW * a.Ci;
-    const int nco = a.Co / 128, nkc = K / 128;
-    const int ntiles = nco * nkc;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile = lid % ntiles, split = lid / ntiles;
-    const int co0 = (tile % nco) * 128, kc0 = (tile / nco) * 128;
-    const int mbeg = split * a.m_per_split;
+    // (a row's offset in its descriptor: row * ld + chunk * 16)
+    const WgradWork w = wgrad_work<128, 128, BR, 1>(a);
+    const int mbeg = w.mbeg, mend = w.mend, nst = w.nst;
     if (mbeg >= a.M) return;
-    const int mend = min(a.M, mbeg + a.m_per_split);
-    const int nst = (mend - mbeg + BR - 1) / BR;
-    const int tap = kc0 / a.Ci, ci0 = kc0 - tap * a.Ci;
-    const int dh = tap / a.KW - a.pad, dw = tap % a.KW - a.pad;
-
-    // descriptors based at the split's first row (dY) / first image (X, or first row when dense), the column offset
-    // (co0 / ci0) in the base: a row's offset is row * ld + chunk * 16, anything at or past row M (dY) out of range
     const int ohw = a.OH * a.OW;
-    const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.OH == a.H && a.OW == a.W;
-    const size_t dro = (size_t)mbeg * a.Co;
-    const __amdgpu_buffer_rsrc_t rd =
-        wg3_rsrc(gD + dro + co0, (uint32_t)min((size_t)a.M * a.Co - dro - co0, (size_t)0x7FFFFFFF));
-    const int img0 = mbeg / ohw;
-    const size_t xro = dense ? (size_t)mbeg * a.Ci : (size_t)img0 * a.H * a.W * a.Ci;
-    const __amdgpu_buffer_rsrc_t rx =
-        wg3_rsrc(gX + xro + ci0, (uint32_t)min((size_t)a.N * a.H * a.W * a.Ci - xro - ci0, (size_t)0x7FFFFFFF));
 
     // this lane's DMA slots: piece j = rows 8 j .. 8 j + 7 of the stage; the lane takes row 8 j + (lane >> 3) and
     // source chunk (lane & 7) ^ swz(row)
@@ -135,24 +115,20 @@ __global__ __launch_bounds__(256, 2) void wgrad_fp8_kernel(const WgradArgs a, co
         char* dX = sX + buf * SI + wid * PP * 1024;
         const int mb = mbeg + is * BR;
 #pragma unroll
-        for (int q = 0; q < PP; ++q) wg3_dma(rd, dD + q * 1024, voffd[q] + (uint32_t)is * dstep);
+        for (int q = 0; q < PP; ++q) buf_dma16(w.rd, dD + q * 1024, voffd[q] + (uint32_t)is * dstep);
 #pragma unroll
         for (int q = 0; q < PP; ++q) {
             const int m = mb + (int)rowx[q];
-            uint32_t off = WG3_OOB;
-            if (dense) {
+            uint32_t off = BUF_OOB;
+            if (w.dense) {
                 if (m < mend) off = (uint32_t)(m - mbeg) * (uint32_t)a.Ci + colx[q];
             } else if (m < mend) {
-                const uint32_t img = fdiv((uint32_t)m, a.mg_ohw, a.sh_ohw);
-                const uint32_t rem = (uint32_t)m - img * (uint32_t)ohw;
-                const uint32_t oh = fdiv(rem, a.mg_ow, a.sh_ow);
-                const uint32_t ow = rem - oh * (uint32_t)a.OW;
-                const int ih = (int)oh * a.stride + dh, iw = (int)ow * a.stride + dw;
-                if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
-                    off = (((img - (uint32_t)img0) * (uint32_t)a.H + (uint32_t)ih) * (uint32_t)a.W + (uint32_t)iw) *
-                              (uint32_t)a.Ci + colx[q];
+                const WgradPix px = wgrad_pix((uint32_t)m, (uint32_t)ohw, (uint32_t)a.OW, a.mg_ohw, a.sh_ohw, a.mg_ow,
+                                              a.sh_ow, a.stride, w.dh, w.dw);
+                if (wgrad_pix_in(px, a.H, a.W))  // (else a padding tap: zeros)
+                    off = wgrad_pix_row<uint32_t>(px, (uint32_t)w.img0, a.H, a.W) * (uint32_t)a.Ci + colx[q];
             }
-            wg3_dma(rx, dX + q * 1024, off);
+            buf_dma16(w.rx, dX + q * 1024, off);
         }
         ++is;
     };
@@ -178,10 +154,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_fp8_kernel(const WgradArgs a, co
     const uint32_t lds0 = (uint32_t)(size_t)(LDS_PTR(char))smem;
     for (int s = 0; s < nst; ++s) {
         if (is - 1 - s >= NS - 2)
-            __builtin_amdgcn_s_waitcnt((((NS - 2) * LPS) & 0xF) | ((((NS - 2) * LPS) >> 4) << 14) | (0x7 << 4) |
-                                       (0xF << 8));
+            wait_vm<(NS - 2) * LPS>();
         else
-            __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));
+            wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         issue();
         const int buf = s % NS;
@@ -222,16 +197,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_fp8_kernel(const WgradArgs a, co
         }
     }
 
-    // acc[i][j][r]: co = co0 + wco*64 + i*16 + (lane>>4)*4 + r ; k = kc0 + wkc*64 + j*16 + (lane&15)
-    const int e = *e_dy + *e_x;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float* dst = a.dW + (size_t)(co0 + wco * 64 + i * 16 + (lane >> 4) * 4 + r) * K + kc0 + wkc * 64 + (lane & 15);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) atomicAdd(dst + j * 16, ldexpf(acc[i][j][r], e));
-        }
+    wgrad_atomic_tile<true>(a.dW + w.kc0 + wkc * 64, w.co0 + wco * 64, a.KH * a.KW * a.Ci, acc, lane, *e_dy + *e_x);
 }
 
 // shapes this kernel covers (host): whole 128-channel tiles of both operands, one image's bytes far below 2^31
@@ -246,19 +212,11 @@ template <int BR, int NS, int MODE>
 int launch_wgrad_fp8(WgradArgs a, const int* e_dy, const int* e_x, int splits, hipStream_t st) {
     const int K = a.KH * a.KW * a.Ci;
     const int ntiles = (a.Co / 128) * (K / 128);
-    if (splits <= 0) {  // one wave of blocks over 256 CUs, two per CU (as launch_wgrad_v3)
-        const int want = (512 + ntiles - 1) / ntiles;
-        const int maxs = (a.M + 4 * BR - 1) / (4 * BR);
-        splits = max(1, min(want, maxs));
-    }
-    int mps = (a.M + splits - 1) / splits;
-    mps = (mps + BR - 1) / BR * BR;  // whole stages: a split's last stage never reads the next split's rows
-    // a split's dY rows / X images addressed by 32-bit offsets from its own base (kernel): keep each below 2^31
-    const size_t ohw = (size_t)a.OH * a.OW, img = (size_t)a.H * a.W * a.Ci;
-    while (mps > BR && ((size_t)mps * a.Co >= (1u << 31) || ((size_t)mps / ohw + 2) * img >= (1u << 31)))
-        mps = (mps / 2 + BR - 1) / BR * BR;
-    splits = (a.M + mps - 1) / mps;
-    a.m_per_split = mps;
+    // 512 blocks: one wave of blocks over 256 CUs, two per CU (as launch_wgrad_v3)
+    const WgradPlan pl =
+        wgrad_plan(a.M, ntiles, BR, 512, splits, (size_t)a.Co, (size_t)a.OH * a.OW, (size_t)a.H * a.W * a.Ci);
+    splits = pl.splits;
+    a.m_per_split = pl.m_per_split;
     const size_t lds = (size_t)NS * 2 * BR * 128;
     hipLaunchKernelGGL((wgrad_fp8_kernel<BR, NS, MODE>), dim3(ntiles * splits), dim3(256), lds, st, a, e_dy, e_x);
     CONV_COUNTED();

@@ -36,11 +36,9 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "conv_wgrad_shared.h"
 
 namespace {
-
-constexpr uint32_t WH_OOB = 0x80000000u;
 
 __device__ __forceinline__ int wh_swz(int q) { return (q >> 1) & 3; }
 
@@ -82,10 +80,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_kernel(const WgradArgs a, i
         const int img = band / bpi, y0 = (band - img * bpi) * R;
         const uint32_t pix0 = (uint32_t)(y0 * W);  // band's first (output) pixel within its image
         const size_t dimg = (size_t)img * a.OH * W * a.Co + co0, ximg = (size_t)img * a.H * a.W * a.Ci + ci0;
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<bf16_t*>(a.dY + dimg), (short)0, (int)min((dall - dimg) * 2, (size_t)0x7FFFFFFF), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<bf16_t*>(a.X + ximg), (short)0, (int)min((xall - ximg) * 2, (size_t)0x7FFFFFFF), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rd = buf_rsrc_n(a.dY + dimg, (dall - dimg) * 2);
+        const __amdgpu_buffer_rsrc_t rx = buf_rsrc_n(a.X + ximg, (xall - ximg) * 2);
 #pragma unroll
         for (int k = 0; k < PPW; ++k) {
             const int piece = wid * PPW + k;
@@ -94,18 +90,16 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_kernel(const WgradArgs a, i
             if (piece < NDY) {
                 const int row = piece * 8 + drow;
                 const uint32_t off = row < BP ? (pix0 + (uint32_t)row) * ldy + (uint32_t)(wh_slot(dslot, row) * 16)
-                                              : WH_OOB;  // padded k rows: zeros
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, (__attribute__((address_space(3))) void*)lds, 16, off, 0,
-                                                         0, 0);
+                                              : BUF_OOB;  // padded k rows: zeros
+                buf_dma16(rd, lds, off);
             } else {
                 const int q = (piece - NDY) * 8 + drow;  // patch row index
                 const int pr = q / PW, pc = q - pr * PW;
                 const int iy = y0 - 1 + pr, ix = pc - 1;
-                uint32_t off = WH_OOB;
+                uint32_t off = BUF_OOB;
                 if ((unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W)
                     off = ((uint32_t)iy * a.W + (uint32_t)ix) * ldx + (uint32_t)(wh_slot(dslot, q) * 16);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (__attribute__((address_space(3))) void*)lds, 16, off, 0,
-                                                         0, 0);
+                buf_dma16(rx, lds, off);
             }
         }
     };
@@ -145,32 +139,24 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_kernel(const WgradArgs a, i
         constexpr int PPW0 = NP - 3 * PPW;  // wave 3's pieces per band (the others issue PPW)
         if (band + 1 < b1) {
             if (wid == 3)
-                __builtin_amdgcn_s_waitcnt((PPW0 & 0xF) | ((PPW0 >> 4) << 14) | (0x7 << 4) | (0xF << 8));
+                wait_vm<PPW0>();
             else
-                __builtin_amdgcn_s_waitcnt((PPW & 0xF) | ((PPW >> 4) << 14) | (0x7 << 4) | (0xF << 8));
+                wait_vm<PPW>();
         } else
-            __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));
+            wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         const char* base = smem + buf * BUF;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             bf16x8 fa[4], fb[9];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(base + adA[ks][0][i]));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(base + adA[ks][1][i]));
-                fa[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int i = 0; i < 4; ++i) fa[i] = tr16_frag(base + adA[ks][0][i], base + adA[ks][1][i]);
 #pragma unroll
             for (int ti = 0; ti < 3; ++ti)
 #pragma unroll
                 for (int tj = 0; tj < 3; ++tj) {
                     const int toff = ti * PW * 128;  // tap row: the window shifted by ti patch rows
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (LDS_PTR(s16x4))(base + adB[ks][0][tj] + toff));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (LDS_PTR(s16x4))(base + adB[ks][1][tj] + toff));
-                    fb[ti * 3 + tj] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                    fb[ti * 3 + tj] = tr16_frag(base + adB[ks][0][tj] + toff, base + adB[ks][1][tj] + toff);
                 }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -179,7 +165,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_halo_kernel(const WgradArgs a, i
                     acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[t], acc[i][t], 0, 0, 0);
         }
         // every wave is done reading this buffer before band + 2 overwrites it
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only (vmcnt 63, expcnt 7)
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();
         if (band + 2 < b1) issue_band(band + 2, buf);
     }

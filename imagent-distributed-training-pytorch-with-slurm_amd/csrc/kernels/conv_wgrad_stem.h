@@ -23,7 +23,7 @@
 
 #pragma once
 
-#include "common.h"
+#include "conv_wgrad_shared.h"
 
 namespace {
 
@@ -149,11 +149,8 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_band_kernel(const WgradArgs
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = 2 * i + (p >> 1);
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (LDS_PTR(s16x4))(sD + px0 * 128 + ((c ^ swg_swz(px0)) << 4) + 8 * (p & 1)));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (LDS_PTR(s16x4))(sD + px1 * 128 + ((c ^ swg_swz(px1)) << 4) + 8 * (p & 1)));
-                fd[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                fd[i] = tr16_frag(sD + px0 * 128 + ((c ^ swg_swz(px0)) << 4) + 8 * (p & 1),
+                                  sD + px1 * 128 + ((c ^ swg_swz(px1)) << 4) + 8 * (p & 1));
             }
             // X fragments: kernel row ks, taps 4h + p (4 channels each) of the pixel's window
             const int ry0 = px0 >= SWG_OW ? px0 / SWG_OW : 0, ox0 = px0 - ry0 * SWG_OW;
@@ -164,11 +161,7 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_band_kernel(const WgradArgs
             for (int k = 0; k < 2; ++k) {
                 const int ks = k ? ks1 : ks0;
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(b0 + ks * SWG_SP + h * 32));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(b1 + ks * SWG_SP + h * 32));
-                    fx[k][h] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-                }
+                for (int h = 0; h < 2; ++h) fx[k][h] = tr16_frag(b0 + ks * SWG_SP + h * 32, b1 + ks * SWG_SP + h * 32);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)

@@ -20,22 +20,15 @@
 //  * NS-deep ring, counted vmcnt + one s_barrier per stage, split-K over m with fp32 atomics into
 //    the gradient arena (as wgrad_kernel), XCD-aware block order: the tiles of one m-range share
 //    an XCD (and its L2).
+// The block decode, the gather, the epilogue (conv_wgrad_shared.h) and the split-K plan (conv_wgrad_plan.h) are
+// shared with the fp8 loop (conv_wgrad_fp8.h); the LDS image, the fragment reads and the MFMA body are this file's.
 
 #pragma once
 
-#include "common.h"
+#include "conv_wgrad_plan.h"
+#include "conv_wgrad_shared.h"
 
 namespace {
-
-constexpr uint32_t WG3_OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg3_rsrc(const void* p, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-__device__ __forceinline__ void wg3_dma(__amdgpu_buffer_rsrc_t r, char* lds, uint32_t voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, 0, 0, 0);
-}
 
 __device__ __forceinline__ int wg3_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
@@ -68,30 +61,11 @@ __global__ __launch_bounds__(WCO * WKC * 64, WCO * WKC == 4 ? 2 : 1) void wgrad_
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wco = wid % WCO, wkc = wid / WCO;
     const int K = a.KH * a.KW * a.Ci;
-    const int nco = (a.Co + TCO - 1) / TCO, nkc = (K + TK - 1) / TK;  // (Co / K = 64: one half-used tile, wgrad_v3_ok)
-    const int ntiles = nco * nkc;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile = lid % ntiles, split = lid / ntiles;
-    const int co0 = (tile % nco) * TCO, kc0 = (tile / nco) * TK;
-    const int mbeg = split * a.m_per_split;
+    // (a row's offset in its descriptor: row * ld * 2 + chunk * 16)
+    const WgradWork w = wgrad_work<TCO, TK, BR, 2>(a);
+    const int co0 = w.co0, kc0 = w.kc0, mbeg = w.mbeg, mend = w.mend, nst = w.nst;
     if (mbeg >= a.M) return;
-    const int mend = min(a.M, mbeg + a.m_per_split);
-    const int nst = (mend - mbeg + BR - 1) / BR;
-    const int tap = kc0 / a.Ci, ci0 = kc0 - tap * a.Ci;
-    const int dh = tap / a.KW - a.pad, dw = tap % a.KW - a.pad;
-
-    // descriptors: the column offset (co0 / ci0) in the base, so a row's offset is row * ld * 2 +
-    // chunk * 16 and anything at or past row M (dY) is out of range. Both are based at the split's first row
-    // (dY) / first image (X, or first row when dense), so the 32-bit offsets hold for any tensor size
     const int ohw = a.OH * a.OW;
-    const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.OH == a.H && a.OW == a.W;
-    const size_t dro = (size_t)mbeg * a.Co;
-    const __amdgpu_buffer_rsrc_t rd =
-        wg3_rsrc(a.dY + dro + co0, (uint32_t)min(((size_t)a.M * a.Co - dro - co0) * 2, (size_t)0x7FFFFFFF));
-    const int img0 = mbeg / ohw;
-    const size_t xro = dense ? (size_t)mbeg * a.Ci : (size_t)img0 * a.H * a.W * a.Ci;
-    const __amdgpu_buffer_rsrc_t rx = wg3_rsrc(
-        a.X + xro + ci0, (uint32_t)min(((size_t)a.N * a.H * a.W * a.Ci - xro - ci0) * 2, (size_t)0x7FFFFFFF));
 
     // this lane's DMA slots: piece j of an operand = sub-image j / (BR / 4), rows 4 (j % (BR / 4)) .. + 3; the lane
     // takes row + prow and source chunk (lane & 15) ^ swz(row) of the sub-image's 128 channels
@@ -120,24 +94,20 @@ __global__ __launch_bounds__(WCO * WKC * 64, WCO * WKC == 4 ? 2 : 1) void wgrad_
         char* dX = sX + buf * SBX + wid * PX * 1024;
         const int mb = mbeg + is * BR;
 #pragma unroll
-        for (int q = 0; q < PD; ++q) wg3_dma(rd, dD + q * 1024, voffd[q] + (uint32_t)is * dstep);
+        for (int q = 0; q < PD; ++q) buf_dma16(w.rd, dD + q * 1024, voffd[q] + (uint32_t)is * dstep);
 #pragma unroll
         for (int q = 0; q < (SYM ? 0 : PX); ++q) {
             const int m = mb + (int)rowx[q];
-            uint32_t off = WG3_OOB;
-            if (dense) {
+            uint32_t off = BUF_OOB;
+            if (w.dense) {
                 if (m < mend) off = (uint32_t)(m - mbeg) * (uint32_t)(a.Ci * 2) + colx[q];
             } else if (m < mend) {
-                const uint32_t img = fdiv((uint32_t)m, a.mg_ohw, a.sh_ohw);
-                const uint32_t rem = (uint32_t)m - img * (uint32_t)ohw;
-                const uint32_t oh = fdiv(rem, a.mg_ow, a.sh_ow);
-                const uint32_t ow = rem - oh * (uint32_t)a.OW;
-                const int ih = (int)oh * a.stride + dh, iw = (int)ow * a.stride + dw;
-                if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
-                    off = (((img - (uint32_t)img0) * (uint32_t)a.H + (uint32_t)ih) * (uint32_t)a.W + (uint32_t)iw) *
-                              (uint32_t)(a.Ci * 2) + colx[q];
+                const WgradPix px = wgrad_pix((uint32_t)m, (uint32_t)ohw, (uint32_t)a.OW, a.mg_ohw, a.sh_ohw, a.mg_ow,
+                                              a.sh_ow, a.stride, w.dh, w.dw);
+                if (wgrad_pix_in(px, a.H, a.W))  // (else a padding tap: zeros)
+                    off = wgrad_pix_row<uint32_t>(px, (uint32_t)w.img0, a.H, a.W) * (uint32_t)(a.Ci * 2) + colx[q];
             }
-            wg3_dma(rx, dX + q * 1024, off);
+            buf_dma16(w.rx, dX + q * 1024, off);
         }
         ++is;
     };
@@ -169,10 +139,9 @@ __global__ __launch_bounds__(WCO * WKC * 64, WCO * WKC == 4 ? 2 : 1) void wgrad_
 
     for (int s = 0; s < nst; ++s) {
         if (is - 1 - s >= NS - 2)
-            __builtin_amdgcn_s_waitcnt((((NS - 2) * LPS) & 0xF) | ((((NS - 2) * LPS) >> 4) << 14) | (0x7 << 4) |
-                                       (0xF << 8));
+            wait_vm<(NS - 2) * LPS>();
         else
-            __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8));
+            wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         issue();
         const int buf = s % NS;
@@ -184,17 +153,9 @@ __global__ __launch_bounds__(WCO * WKC * 64, WCO * WKC == 4 ? 2 : 1) void wgrad_
         for (int ks = 0; ks < NKS; ++ks) {
             bf16x8 fd[4], fx[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(bD + ks * 8192 + offa[i][0]));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(bD + ks * 8192 + offa[i][1]));
-                fd[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int i = 0; i < 4; ++i) fd[i] = tr16_frag(bD + ks * 8192, offa[i][0], offa[i][1]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(bX + ks * 8192 + offb[j][0]));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(bX + ks * 8192 + offb[j][1]));
-                fx[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int j = 0; j < 4; ++j) fx[j] = tr16_frag(bX + ks * 8192, offb[j][0], offb[j][1]);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -205,26 +166,11 @@ __global__ __launch_bounds__(WCO * WKC * 64, WCO * WKC == 4 ? 2 : 1) void wgrad_
 
     // acc[i][j][r]: co = co0 + wco*64 + i*16 + (lane>>4)*4 + r ; k = kc0 + wkc*64 + j*16 + (lane&15)
     if (kc0 + wkc * 64 >= K || co0 + wco * 64 >= a.Co) return;
-    if constexpr (SYM == 2) {
-        if (wco != wkc) return;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float* dst = a.dW + (size_t)(i * 16 + (lane >> 4) * 4 + r) * 64 + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) atomicAdd(dst + j * 16, acc[i][j][r]);
-            }
-        return;
+    if constexpr (SYM == 2) {  // both diagonal waves into the one 64 x 64 output
+        if (wco == wkc) wgrad_atomic_tile(a.dW, 0, 64, acc, lane);
+    } else {
+        wgrad_atomic_tile(a.dW + kc0 + wkc * 64, co0 + wco * 64, K, acc, lane);
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float* dst = a.dW + (size_t)(co0 + wco * 64 + i * 16 + (lane >> 4) * 4 + r) * K + kc0 + wkc * 64 + (lane & 15);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) atomicAdd(dst + j * 16, acc[i][j][r]);
-        }
 }
 
 // shapes this kernel covers (host): one tap per 128-wide k tile, whole 128-channel co tiles,
@@ -253,6 +199,7 @@ int launch_wgrad_v3(WgradArgs a, int splits, hipStream_t st) {
     constexpr int TCO = 64 * WCO, TK = 64 * WKC;
     const int K = a.KH * a.KW * a.Ci;
     const int ntiles = ((a.Co + TCO - 1) / TCO) * ((K + TK - 1) / TK);
+    int target = 512;
     if (splits <= 0) {
         // one wave of blocks over 256 CUs (two per CU for the 4-wave tile): the 1x1 wgrads are split-K streams whose
         // second, partial wave of blocks cost more than the extra atomics of deeper splits save (same-box bench:
@@ -260,23 +207,13 @@ int launch_wgrad_v3(WgradArgs a, int splits, hipStream_t st) {
         // (16-wave tile: IMAGENT_WGRAD_WIDE_TARGET blocks, A/B -- fewer than one per CU leaves CUs to the main
         // stream's small kernels, which otherwise wait for a slot behind the one-block-per-CU side-stream grid; measured
         // at 4096 img: 256 17,899 / 17,805, 192 17,805 / 17,790, 128 17,749 / 17,755 img/s -- one per CU stays)
-        static const int wide_target = [] {
-            const char* e = getenv("IMAGENT_WGRAD_WIDE_TARGET");
-            return e && atoi(e) > 0 ? atoi(e) : 256;
-        }();
-        const int target = WCO * WKC == 4 ? 512 : wide_target;
-        const int want = (target + ntiles - 1) / ntiles;
-        const int maxs = (a.M + 4 * BR - 1) / (4 * BR);
-        splits = max(1, min(want, maxs));
+        static const long wide_target = env_int("IMAGENT_WGRAD_WIDE_TARGET", 256);
+        if (WCO * WKC != 4) target = wide_target > 0 ? (int)wide_target : 256;
     }
-    int mps = (a.M + splits - 1) / splits;
-    mps = (mps + BR - 1) / BR * BR;  // whole stages: a split's last stage never reads the next split's rows
-    // a split's dY rows / X images addressed by 32-bit offsets from its own base (kernel): keep each below 2^31
-    const size_t ohw = (size_t)a.OH * a.OW, img = (size_t)a.H * a.W * a.Ci * 2;
-    while (mps > BR && ((size_t)mps * a.Co * 2 >= (1u << 31) || ((size_t)mps / ohw + 2) * img >= (1u << 31)))
-        mps = (mps / 2 + BR - 1) / BR * BR;
-    splits = (a.M + mps - 1) / mps;
-    a.m_per_split = mps;
+    const WgradPlan pl = wgrad_plan(a.M, ntiles, BR, target, splits, (size_t)a.Co * 2, (size_t)a.OH * a.OW,
+                                    (size_t)a.H * a.W * a.Ci * 2);
+    splits = pl.splits;
+    a.m_per_split = pl.m_per_split;
     const size_t lds = (size_t)NS * ((TCO + 127) / 128 + (SYM ? 0 : (TK + 127) / 128)) * BR * 256;
     hipLaunchKernelGGL((wgrad_v3_kernel<BR, NS, WCO, WKC, SYM>), dim3(ntiles * splits), dim3(WCO * WKC * 64), lds, st, a);
     CONV_COUNTED();

@@ -282,6 +282,9 @@ def _declare(name: str, lib) -> None:
         lib.imr_records_submit.restype = i32
         lib.imr_records_wait.argtypes = [vp, i32]
         lib.imr_records_wait.restype = i32
+        # the weight-gradient launchers' split-K plan (csrc/kernels/conv_wgrad_plan.h via csrc/runtime/wgrad_plan.cpp)
+        lib.imr_wgrad_plan.argtypes = [i32, i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]
+        lib.imr_wgrad_plan.restype = i32
 
 
 STAT_SLOTS = 32  # conv epilogue statistics slab depth (csrc/kernels/conv_igemm.hip)
