@@ -89,6 +89,7 @@ IMK_EXPORT int imk_conv_igemm(const IGemmArgs* args, int tile, void* stream) {
                                  !a.bnsave || !a.stats || (!a.bnym && (!a.bngamma || !a.bnbeta)) ||
                                  (a.bnx2 && !a.bnsave2)))
         return -104;
+    if ((a.flags & IG_NEXT1) && ((a.flags & IG_STEM) || a.xbn || a.X2 || tile != 0)) return -122;
     if (a.flags & IG_STEM) {  // C == 4 row-segment gather, K = KH x 32
         if (a.C != 4 || a.ntw > 8 || a.dhs != 1 || a.dws != 1) return -102;
         if (tile == 0 || tile == 23) {  // band stem (tile 0) / streaming row-segment stem (23), conv_stream.hip
@@ -135,7 +136,7 @@ IMK_EXPORT int imk_conv_igemm(const IGemmArgs* args, int tile, void* stream) {
         const int r = conv_stream(a, st, bn_hint);
         if (r != 1) return r;
     }
-    if (a.flags & (IG_RES | IG_MASKOUT | IG_Q8OUT)) return -121;  // only the streaming kernel has that epilogue
+    if (a.flags & (IG_RES | IG_MASKOUT | IG_Q8OUT | IG_NEXT1)) return -121;  // only the streaming kernel has that epilogue
     if (autotile) tile = (a.Nout <= 64) ? 4 : 2;
     // measured on MI355X (profiles/r50_conv_layers_*): the register-staged
     // pipeline wins for 64-wide output tiles and single-stage (K <= 64) tiles,

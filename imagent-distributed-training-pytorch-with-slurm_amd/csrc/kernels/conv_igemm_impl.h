@@ -102,6 +102,15 @@ struct IGemmArgs {
     void* Y8;
     const int* y8exp;
     float* y8amax;
+    // IG_NEXT1 (streaming 1x1 fused-output kernel, K = 64 into Nout = 256 only): also the NEXT 1x1 stride-1 conv on
+    // the stored output, Y2 [M][Co2] = Y [M][Nout] x W2^T with W2 [Co2][ldb2] (the following bottleneck's conv1),
+    // bit-identical to that conv run on Y; its shifted forward statistics go to stats2 [STAT_SLOTS][2][Co2] around
+    // shift2 [Co2] (either may be null, as stats / shift)
+    const bf16_t* W2;
+    bf16_t* Y2;
+    float* stats2;
+    const float* shift2;
+    int Co2, ldb2;
 };
 
 #define IG_OUT_F32 1   // fp32 output (else bf16)
@@ -122,6 +131,8 @@ struct IGemmArgs {
 #define IG_Q8OUT 32768  // (streaming 1x1 only) also the e4m3 copy of the output (Y8 / y8exp / y8amax)
 #define IG_MASKOUT 16384  // (streaming 1x1 only, with IG_RELU) also write the ReLU mask of the stored output as bits
                           // into bnym (byte e / 8, bit e % 8; bn.hip bn_fwd's `ym` format)
+#define IG_NEXT1 65536  // (streaming 1x1 only, with IG_RES / IG_MASKOUT) also the next 1x1 conv of the stored output
+                        // (W2 / Y2 / stats2 / shift2 / Co2 / ldb2)
 #define STAT_SLOTS 32  // stats slab: [STAT_SLOTS][2][Nout]
 
 static __device__ __attribute__((aligned(64))) uint32_t g_igemm_zero[16];  // zero line for masked DMA lanes (per TU)
@@ -441,6 +452,13 @@ __host__ __device__ constexpr int epi_swz(int row, int byte) { return byte ^ ((r
 __device__ __forceinline__ u32x4 epi_read(const char* base, int row, int pitch, int cc) {
     const u32x4 t = *reinterpret_cast<const u32x4*>(base + row * pitch + ((cc * 16) ^ ((row & 14) << 3)));
     return (row & 1) ? u32x4{t[2], t[3], t[0], t[1]} : t;
+}
+
+// ... and its inverse: chunk cc of row r back into the swizzled tile (conv_stream.hip: the stored output as the next
+// conv's operand)
+__device__ __forceinline__ void epi_write(char* base, int row, int pitch, int cc, u32x4 v) {
+    *reinterpret_cast<u32x4*>(base + row * pitch + ((cc * 16) ^ ((row & 14) << 3))) =
+        (row & 1) ? u32x4{v[2], v[3], v[0], v[1]} : v;
 }
 
 // per-(quantity, channel-in-chunk) block stride of the statistics fold image [nq][8][RG][CPR] (floats): padded so

@@ -61,8 +61,21 @@ constexpr int stream_rp() {  // LDS weight row pitch in 16-B chunks: 16-chunk sw
     return STEM ? 32 : (KT / 8 <= 16 ? KT / 8 : (KT / 8 + 15) / 16 * 16);
 }
 
+// MODE 5 (IG_NEXT1): MODE 4 whose block also computes the NEXT 1x1 conv on the output it stores -- Y2[M][CO2] =
+// out[M][BN] x W2^T, the following bottleneck's conv1 -- from the wave-private epilogue tile, with that conv's
+// shifted forward statistics (stats2 / shift2): the widest tensor of the block is not read back from HBM. Single
+// slice only (BN = Nout: a wave holds every channel of its pixels). W2 [CO2][BN] is a second LDS-resident weight
+// image, so two 4-wave blocks no longer fit a CU: NW = 8 waves share both images (one block per CU, the same 8
+// waves and 256 VGPRs per wave; stream_nw / stream_co2 below). The second GEMM runs k-steps ascending per
+// accumulator on the stored bf16 bits, as conv_stream_kernel<256, 64, 2, 0> does on `out`: Y2 is bit-identical to
+// the stand-alone conv
+// (the template's parameter list stays as it was: the kernel names are what profiles and tests know them by)
+constexpr int stream_nw(int mode) { return mode == 5 ? 8 : 4; }    // waves per block
+constexpr int stream_co2(int mode) { return mode == 5 ? 64 : 0; }  // the next conv's output channels
+
 template <int K, int BN, int D, int MODE, bool STEM = false, bool XBN = false, int K2 = 0>
-__global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) {
+__global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(const IGemmArgs a) {
+    constexpr int NW = stream_nw(MODE), CO2 = stream_co2(MODE);
     constexpr int KS1 = K / 32;       // k-steps from X
     constexpr int KS = (K + K2) / 32; // MFMA k-steps per group
     constexpr int FN = BN / 16;       // channel fragments
@@ -75,7 +88,12 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
     constexpr int PPR = 64 / CH;      // pixels per epilogue read instruction
     constexpr int NR = 16 / PPR;      // epilogue reads per 16-pixel group
     constexpr bool bnb = MODE >= 1 && MODE <= 3, has_y = MODE == 1 || MODE == 3, has_x2 = MODE == 3;
-    constexpr bool FO = MODE == 4;
+    constexpr bool FO = MODE == 4 || MODE == 5, NX = MODE == 5;
+    constexpr int RB2 = BN * 2;        // W2 row pitch in LDS (bytes): BN / 8 chunks, swizzled in groups of 16
+    constexpr int FN2 = CO2 / 16;      // channel fragments of the second output
+    constexpr int EP2 = CO2 * 2, CH2 = NX ? CO2 / 8 : 1, PPR2 = 64 / CH2, NR2 = NX ? 16 / PPR2 : 0;
+    static_assert(!NX || (K2 == 0 && !STEM && !XBN && BN == 256 && (CO2 == 64 || CO2 == 128)), "next-conv mode");
+    static_assert(NX || CO2 == 0, "CO2: next-conv mode only");
     // chunks whose global reads are batched; with the BN-backward epilogue all
     // of a group's reads (x, y | x2, old) are issued before its MFMAs
     constexpr int QB = bnb ? NR : (NR < 4 ? NR : 4);
@@ -83,7 +101,8 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     char* sW = smem;
-    char* sE = smem + BN * RB + wid * 16 * EP;
+    char* sW2 = smem + BN * RB;  // (NX) the next conv's weights [CO2][BN]
+    char* sE = smem + BN * RB + CO2 * RB2 + wid * 16 * EP;
 
     const int nsl = a.Nout / BN;
     const int G = gridDim.x;  // multiple of nsl (host)
@@ -93,10 +112,17 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
     const bool accum = a.flags & IG_ACCUM;
 
     // weight slice -> LDS: chunk c of row r at slot c ^ (r & SWM)
-    for (int idx = tid; idx < BN * CPR; idx += 256) {
+    for (int idx = tid; idx < BN * CPR; idx += NW * 64) {
         const int r = idx / CPR, c = idx % CPR;
         const u32x4 v = *reinterpret_cast<const u32x4*>(a.Wk + (size_t)(n0 + r) * a.ldb + c * 8);
         *reinterpret_cast<u32x4*>(sW + r * RB + ((c ^ (r & SWM)) * 16)) = v;
+    }
+    if constexpr (NX) {
+        for (int idx = tid; idx < CO2 * (BN / 8); idx += NW * 64) {
+            const int r = idx / (BN / 8), c = idx % (BN / 8);
+            const u32x4 v = *reinterpret_cast<const u32x4*>(a.W2 + (size_t)r * a.ldb2 + c * 8);
+            *reinterpret_cast<u32x4*>(sW2 + r * RB2 + ((c ^ (r & 15)) * 16)) = v;
+        }
     }
 
     // fixed epilogue channel chunk of this lane + the BN constants it needs
@@ -146,6 +172,8 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             mean[c] = (a.stats && a.shift) ? a.shift[n + c] : 0.f;
+            // (NX: the first output has no statistics; mean / s1 / s2 serve the second output's channel chunk)
+            if constexpr (NX) mean[c] = (a.stats2 && a.shift2) ? a.shift2[(lane % CH2) * 8 + c] : 0.f;
             sc[c] = affine ? a.bias[n + c] : 1.f;
             sh[c] = affine ? a.bias[a.Nout + n + c] : 0.f;
             rsc[c] = resaff ? a.bnsave2[n + c] : 1.f;
@@ -163,8 +191,8 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
     const int ohw = a.OH * a.OW;
     const bool dense = a.sA == 1 && a.H == a.OH && a.W == a.OW;  // input row == output pixel
     const int ngroups = (a.M + 15) / 16;
-    const int wstride = npb * 4;
-    const int w0 = pb * 4 + wid;
+    const int wstride = npb * NW;
+    const int w0 = pb * NW + wid;
     const int fr = lane & 15, fq = lane >> 4;
 
     u32x4 pf[D][KS];
@@ -290,6 +318,11 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
     int aoff[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) aoff[ks] = fr * RB + (((ks * 4 + fq) ^ (fr & SWM)) * 16);
+    // W2 A fragments: chunk ks * 4 + fq of row fr at slot (ks * 4 + fq) ^ fr; the swizzle leaves ks / 4 alone, so
+    // four offsets (ks % 4) serve the eight k-steps
+    int aoff2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) aoff2[j] = fr * RB2 + (((j * 4 + fq) ^ fr) * 16);
     float xsc[XBN ? KS : 1][8], xsh[XBN ? KS : 1][8];  // this lane's channels ks * 32 + fq * 8 + e
     if constexpr (XBN) {
 #pragma unroll
@@ -445,6 +478,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
 #pragma unroll
                     for (int k = 0; k < 4; ++k) o[k] = pack_bf2(v[2 * k], v[2 * k + 1]);
                     __builtin_amdgcn_raw_buffer_store_b128(o, eb.ry, o2[q], 0, 0);
+                    if constexpr (NX) epi_write(sE, p, EP, cc, o);  // the stored bits: the next conv's pixel operand
                     if (q8out) {  // quantise the bf16-rounded values the bf16 consumers see
                         float w[8];
 #pragma unroll
@@ -468,7 +502,7 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
                         }
                         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)b, eb.rym, ev[q] ? o2[q] / 16 : BUF_OOB, 0, 0);
                     }
-                    if (a.stats) {
+                    if (!NX && a.stats) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {  // statistics of the stored (bf16) values
                             v[2 * k] = lo_bf(o[k]) * vf;
@@ -499,12 +533,88 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
                 }
             }
             __builtin_amdgcn_wave_barrier();
-            if constexpr (EPF) issue_early(d, g + D * wstride);
+            if constexpr (NX) {
+                // (the epilogue operands' registers are free again: the next group's go out under the second GEMM)
+                if constexpr (EPF) issue_early(d, g + D * wstride);
+                // the next conv on the tile just stored: B fragment of k-step ks = chunk ks * 4 + fq of pixel row fr
+                bf16x8 fb2[BN / 32];
+#pragma unroll
+                for (int ks = 0; ks < BN / 32; ++ks)
+                    fb2[ks] = __builtin_bit_cast(bf16x8, epi_read(sE, fr, EP, ks * 4 + fq));
+                f32x4 acc2[FN2];
+#pragma unroll
+                for (int i = 0; i < FN2; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                constexpr int NT2 = (BN / 32) * FN2, RR2 = 8;
+                auto w2frag = [&](int t) {  // MFMA t = (k-step t / FN2, channel fragment t % FN2)
+                    return *reinterpret_cast<const bf16x8*>(sW2 + (t % FN2) * 16 * RB2 + aoff2[(t / FN2) & 3] +
+                                                            ((t / FN2) >> 2) * 256);
+                };
+                bf16x8 fa2[RR2];
+#pragma unroll
+                for (int t = 0; t < RR2 - 1; ++t) fa2[t] = w2frag(t);
+                __builtin_amdgcn_sched_group_barrier(0x100, RR2 - 1, 0);
+#pragma unroll
+                for (int t = 0; t < NT2; ++t) {
+                    if (t + RR2 - 1 < NT2) {
+                        fa2[(t + RR2 - 1) % RR2] = w2frag(t + RR2 - 1);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
+                    acc2[t % FN2] =
+                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa2[t % RR2], fb2[t / FN2], acc2[t % FN2], 0, 0, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                }
+                // second output through the same wave-private tile (every fb2 read above is complete: the
+                // accumulators depend on them): 16 x CO2 bf16, rows of EP2 bytes, then coalesced 16-B row chunks
+#pragma unroll
+                for (int i = 0; i < FN2; ++i)
+                    *reinterpret_cast<u32x2*>(sE + fr * EP2 + epi_swz(fr, (i * 16 + fq * 4) * 2)) =
+                        u32x2{pack_bf2(acc2[i][0], acc2[i][1]), pack_bf2(acc2[i][2], acc2[i][3])};
+                __builtin_amdgcn_wave_barrier();
+                const __amdgpu_buffer_rsrc_t ry2 = buf_rsrc(a.Y2 + (size_t)(g < ngroups ? g * 16 : 0) * CO2, true);
+#pragma unroll
+                for (int q = 0; q < NR2; ++q) {
+                    const int p = q * PPR2 + lane / CH2, c2 = lane % CH2;
+                    const bool ev2 = g < ngroups && g * 16 + p < a.M;
+                    const u32x4 t = epi_read(sE, p, EP2, c2);
+                    __builtin_amdgcn_raw_buffer_store_b128(t, ry2, ev2 ? (uint32_t)(p * CO2 + c2 * 8) * 2 : BUF_OOB, 0, 0);
+                    if (a.stats2) {  // shifted sums of the stored values, as the plain epilogue's
+                        const float vf = ev2 ? 1.f : 0.f;
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) {
+                            const float v = (c & 1 ? hi_bf(t[c >> 1]) : lo_bf(t[c >> 1])) * vf;
+                            const float dd = (v - mean[c]) * vf;
+                            s1[c] += dd;
+                            s2[c] += dd * dd;
+                        }
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+            if constexpr (EPF && !NX) issue_early(d, g + D * wstride);
         }
     }
     if (q8out) {  // one atomic per wave into the 32-slot amax row
         m8 = wave_max(m8);
         if (lane == 0) atomic_max_pos(a.y8amax + (blockIdx.x & 31), m8);
+    }
+    if constexpr (NX) {  // the second output's statistics (the first has none in this mode)
+        if (!a.stats2) return;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+#pragma unroll
+            for (int o = CH2; o < 64; o <<= 1) {
+                s1[c] += __shfl_xor(s1[c], o, 64);
+                s2[c] += __shfl_xor(s2[c], o, 64);
+            }
+        }
+        if (lane >= CH2) return;
+        float* st2 = a.stats2 + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 2 * CO2 + lane * 8;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            atomicAdd(st2 + c, s1[c]);
+            atomicAdd(st2 + CO2 + c, s2[c]);
+        }
+        return;
     }
     if (!a.stats) return;
     // fold the lanes that share a channel chunk, one atomic per channel and quantity
@@ -529,15 +639,24 @@ __global__ __launch_bounds__(256, 2) void conv_stream_kernel(const IGemmArgs a) 
 
 template <int K, int BN, int D, int MODE, bool STEM = false, bool XBN = false, int K2 = 0>
 int launch_stream1(const IGemmArgs& a, hipStream_t st) {
+    constexpr int NW = stream_nw(MODE), CO2 = stream_co2(MODE);
     constexpr int RP = stream_rp<STEM, K + K2>();
-    const size_t lds = (size_t)BN * RP * 16 + 4 * 16 * (BN * 2);
+    // weight slice (+ the next conv's [CO2][BN] image) + one 16-pixel epilogue tile per wave
+    const size_t lds = (size_t)BN * RP * 16 + (size_t)CO2 * BN * 2 + NW * 16 * (BN * 2);
+    const auto kern = conv_stream_kernel<K, BN, D, MODE, STEM, XBN, K2>;
     static int resident = 0;
-    if (resident == 0) resident = resident_blocks(conv_stream_kernel<K, BN, D, MODE, STEM, XBN, K2>, lds);
+    if (resident == 0) {
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds) != hipSuccess)
+            return -123;
+        resident = resident_blocks(kern, lds, NW * 64);
+    }
     const int nsl = a.Nout / BN;
     const int ngroups = (a.M + 15) / 16;
     // enough pixel blocks to fill the chip, but >= D groups per wave
-    const int npb = std::max(1, std::min(resident / nsl, (ngroups + 4 * D - 1) / (4 * D)));
-    hipLaunchKernelGGL((conv_stream_kernel<K, BN, D, MODE, STEM, XBN, K2>), dim3(npb * nsl), dim3(256), lds, st, a);
+    const int npb = std::max(1, std::min(resident / nsl, (ngroups + NW * D - 1) / (NW * D)));
+    hipLaunchKernelGGL(kern, dim3(npb * nsl), dim3(NW * 64), lds, st, a);
     CONV_COUNTED();
     IMK_CHECK_LAUNCH();
     return 0;
@@ -769,6 +888,22 @@ int conv_stream(const IGemmArgs& a, hipStream_t st, int bn) {
          ((a.flags & IG_MASKOUT) && (!a.bnym || !(a.flags & IG_RELU))) ||
          ((a.flags & IG_Q8OUT) && (!a.Y8 || !a.y8exp || !a.y8amax))))
         return -121;
+    // IG_NEXT1: the fused-output kernel's single-slice form only (K = 64 into 256 channels on the same pixels, no
+    // e4m3 copy), the next conv into 64 channels; anything else is an error, never another kernel
+    if (a.flags & IG_NEXT1) {
+        // (Co2 = 128, layer 1 into layer 2: a 64-KB W2 image and all 160 KB of a CU's LDS; built and measured, 1.2 ms
+        // less stand-alone but in-step within the noise, profiles/ab/next_conv1.txt: not kept)
+        if (!(a.flags & (IG_RES | IG_MASKOUT)) ||
+            (a.flags & (IG_Q8OUT | IG_OUT_F32 | IG_FP8 | IG_REGSTAGE | IG_NOSTREAM)) || a.stats || a.xbn || a.X2 ||
+            a.C != 64 || a.Nout != 256 || (bn != 0 && bn != 256) || !a.W2 || !a.Y2 || a.Co2 != 64 || a.ldb2 < 256 ||
+            a.ldb2 % 8 || a.nth != 1 || a.ntw != 1 || a.sA != 1 || a.H != a.OH || a.W != a.OW || a.dh0 != 0 ||
+            a.dw0 != 0 || a.kh0 != 0 || a.kw0 != 0 || a.sY != 1 || a.oy != 0 || a.ox != 0 || a.YH != a.OH ||
+            a.YW != a.OW || a.ldy != a.Nout || a.ldb < a.C)
+            return -122;
+        // D = 1 (2 spills 26 VGPRs); the next group's residual rows are then prefetched too (EPF), issued before
+        // the second GEMM
+        return launch_stream1<64, 256, 1, 5>(a, st);
+    }
     const bool has_bias = a.bias && !eval_bn;
     if (a.X2) {
         // the Gram-form conv3 dgrad of a 64-channel bottleneck (bn_gram.hip): K = [g (256) | h2 (64)] into 64

@@ -57,6 +57,9 @@ class NativeState:
             object.__setattr__(b, "_prev_block", blocks[k - 1] if k > 0 else None)
             b._fuse_bnb = bnb_fusion
             b._has_next = k + 1 < len(blocks)  # a next block whose conv1 dgrad finishes this block's last BN
+            # (forward: conv3's fused-output launch may compute the next block's conv1, ops/block.py _next1_target)
+            object.__setattr__(b, "_next_block", blocks[k + 1] if k + 1 < len(blocks) else None)
+            b._next1_in = None
             b._last_bn = None
             b._bnb_done = False
         self._bind_shadows()

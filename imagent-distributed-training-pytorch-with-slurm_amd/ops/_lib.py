@@ -92,6 +92,8 @@ class IGemmArgs(C.Structure):
         ("xbn", C.c_void_p),
         ("X2", C.c_void_p), ("C2", C.c_int),
         ("Y8", C.c_void_p), ("y8exp", C.c_void_p), ("y8amax", C.c_void_p),
+        ("W2", C.c_void_p), ("Y2", C.c_void_p), ("stats2", C.c_void_p), ("shift2", C.c_void_p),
+        ("Co2", C.c_int), ("ldb2", C.c_int),
     ]
 
 

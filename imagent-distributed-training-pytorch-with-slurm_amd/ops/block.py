@@ -27,6 +27,7 @@ It also removes ~6 autograd nodes and their Python dispatch per block.
 from __future__ import annotations
 
 import os
+import weakref
 
 import torch
 
@@ -81,6 +82,24 @@ _GRAM_MAX_P = 256
 # applies bn3 + shortcut + ReLU and writes the block output and its mask bits: x3 is never written or read
 # (IMAGENT_BN_GRAM_FWD=0: off, A/B)
 _GRAM_FWD = os.environ.get("IMAGENT_BN_GRAM_FWD", "1") != "0"
+# IMAGENT_NEXT_CONV1 (default 1; 0 = A/B off): where conv3's fused-output epilogue writes a 256-channel block output
+# from K = 64 (ResNet-50's layer 1), the same kernel also computes the NEXT block's conv1 (256 -> 64, 1x1) and its
+# BatchNorm statistics from the tile it has just stored (conv_stream.hip IG_NEXT1), bit-identical to the conv run
+# on the output: the next block's forward takes that result instead of reading the block output back from HBM
+_NEXT1 = os.environ.get("IMAGENT_NEXT_CONV1", "1") != "0"
+
+
+def _next1_target(block, conv, q):
+    """The next block's (conv1, bn1) when conv3's fused-output launch can compute that conv too, else None."""
+    nb = getattr(block, "_next_block", None)
+    if not _NEXT1 or nb is None or q is not None or _conv.deterministic():
+        return None
+    c1, b1, _ = nb.convs_bns()[0]
+    if not (conv.in_channels == 64 and conv.out_channels == 256 and c1.kh == 1 and c1.kw == 1 and c1.stride == 1
+            and c1.padding == 0 and c1.in_channels == 256 and c1.out_channels == 64
+            and not getattr(c1, "stem", False)):
+        return None
+    return c1, b1
 
 
 def _gram_ok(block, q, x) -> bool:
@@ -216,6 +235,15 @@ class BlockFn(torch.autograd.Function):
         saved = [x]
         h, h8 = x, x8
         ds = block.downsample
+        # conv1's output as the previous block's conv3 launch left it (IMAGENT_NEXT_CONV1), valid only for the very
+        # tensor it was computed from; after any other input, bn1's slab holds that launch's sums: cleared
+        a1, stash = None, getattr(block, "_next1_in", None)
+        block._next1_in = None
+        if stash is not None:
+            if stash[0]() is x:
+                a1 = stash[1]
+            else:
+                _lib.zero_(pairs[0][1].work.slab)
         # --fp8-wgrad: the e4m3 input copies (conv index / "ds" -> (bytes, exponent view)) kept for the backward pass
         wg8 = {}
         if ds is not None and _keep8(q, ds[0], x8) is not None:
@@ -233,8 +261,11 @@ class BlockFn(torch.autograd.Function):
         ss = None
         h2sum = None  # Gram form: colsum(h2), accumulated by the BN pass that writes h2
         for i, (conv, bn, _) in enumerate(pairs[:-1]):
-            a = _fwd8(conv, h, h8, bn) if ss is None else \
-                igemm_fwd(h, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw, stats=bn.work, xbn=ss)
+            if i == 0 and a1 is not None:
+                a = a1
+            else:
+                a = _fwd8(conv, h, h8, bn) if ss is None else \
+                    igemm_fwd(h, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw, stats=bn.work, xbn=ss)
             if ss is None and _keep8(q, conv, h8) is not None:
                 wg8[i] = _keep8(q, conv, h8)
             ss = None
@@ -282,8 +313,14 @@ class BlockFn(torch.autograd.Function):
             # e4m3 copy from the same epilogue when an fp8 conv reads it
             ym = torch.empty(out.numel() // 8, device=out.device, dtype=torch.uint8)
             q8 = q.out_for(out, q.slot[id(bn)]) if need8 else None
-            igemm_fwd(h, conv.w_bf16, 1, 0, 1, 1, out=out, affine=aff, relu=True, res=res, maskout=ym, res_scale=rsc,
-                      q8out=q8)
+            nxt = _next1_target(block, conv, q)
+            if nxt is not None:
+                _, a1n = igemm_fwd(h, conv.w_bf16, 1, 0, 1, 1, out=out, affine=aff, relu=True, res=res, maskout=ym,
+                                   res_scale=rsc, next1=(nxt[0].w_bf16, nxt[1].work))
+                block._next_block._next1_in = (weakref.ref(out), a1n)
+            else:
+                igemm_fwd(h, conv.w_bf16, 1, 0, 1, 1, out=out, affine=aff, relu=True, res=res, maskout=ym,
+                          res_scale=rsc, q8out=q8)
             a = None
         elif ss is not None:
             a = igemm_fwd(h, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw, stats=bn.work, xbn=ss)

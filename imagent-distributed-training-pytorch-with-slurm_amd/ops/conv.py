@@ -142,7 +142,7 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
               fp8: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, affine: Optional[torch.Tensor] = None,
               accumulate: bool = False, xbn: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
               maskout: Optional[torch.Tensor] = None, res_scale: Optional[torch.Tensor] = None,
-              q8out=None) -> torch.Tensor:
+              q8out=None, next1=None):
     """y[N,OH,OW,Co] = conv(x[N,H,W,Ci], w[Co,KH,KW,Ci]) (+bias) (ReLU); optional
     per-channel (sum, sumsq) accumulation into ``stats`` (a [STAT_SLOTS, 2, Co]
     slab), or, given a BatchNorm workspace (``bn.work``), into its slab as
@@ -163,7 +163,11 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
     shortcut + ReLU in the conv's epilogue); ``maskout`` (uint8, numel / 8): also the ReLU mask of the stored
     output as bits; ``res_scale`` (fp32 [Co]): the residual enters as res * res_scale (a downsample block's
     shortcut BatchNorm, its shift folded into ``affine``); ``q8out`` = (y8 uint8 like ``out``, exponent int32[1],
-    amax fp32[32]): also the delayed-scaled e4m3 copy of the output. All four: the streaming 1x1 kernel only."""
+    amax fp32[32]): also the delayed-scaled e4m3 copy of the output. All four: the streaming 1x1 kernel only.
+    ``next1`` = (w2 [Co2, 1, 1, Co] bf16, stats2): with ``res`` / ``maskout`` on the 64 -> 256 streaming kernel, the
+    same launch also computes the NEXT 1x1 stride-1 conv of the stored output, ``igemm_fwd(out, w2, 1, 0, 1, 1,
+    stats=stats2)`` bit for bit (a following bottleneck's conv1; ``stats2`` as ``stats``, or None), without reading
+    ``out`` back; returns ``(out, y2)``. A shape that kernel does not cover raises (no other kernel is tried)."""
     N, H, W, Ci = x.shape
     Co = w.shape[0]
     OH, OW = conv_out_size(H, KH, stride, pad), conv_out_size(W, KW, stride, pad)
@@ -208,6 +212,20 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
     if xbn is not None:
         assert xbn.shape == (2, Ci) and xbn.dtype == torch.float32 and xbn.is_contiguous()
         a.xbn = xbn.data_ptr()
+    y2 = None
+    if next1 is not None:
+        w2, st2 = next1
+        assert w2.dtype == torch.bfloat16 and w2.is_contiguous() and w2.numel() == w2.shape[0] * Co and stats is None
+        assert not _DET, "next1: statistics from the epilogue's atomics only"
+        y2 = torch.empty((N, OH, OW, w2.shape[0]), device=x.device, dtype=torch.bfloat16)
+        a.flags |= 65536
+        a.W2, a.Y2, a.Co2, a.ldb2 = w2.data_ptr(), y2.data_ptr(), w2.shape[0], Co
+        if st2 is not None:
+            if hasattr(st2, "slab"):  # a BatchNorm's workspace, as ``stats`` below
+                if _SHIFT:
+                    a.shift2 = st2.save.data_ptr()
+                st2 = st2.slab
+            a.stats2 = st2.data_ptr()
     det = None
     if stats is not None:
         if hasattr(stats, "slab"):  # a BatchNorm's workspace: shifted sums around its last batch mean
@@ -225,6 +243,8 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
         part = torch.empty(k.imk_bn_stats_det_floats(R, Co), device=out.device, dtype=torch.float32)
         _lib.check(k.imk_bn_stats_det(out.data_ptr(), det[1], det[0].data_ptr(), part.data_ptr(), R, Co,
                                       _lib.stream_ptr()), "bn stats (deterministic)")
+    if next1 is not None:
+        return out, y2
     return out
 
 
