@@ -7,7 +7,8 @@ below 2^23 (exact fp32 partial sums in any order). The existing relative-L2 chec
 batch and allow 1e-3 on the statistics; here a row written or counted twice, a padding tap that is not zero or a
 tile past its image range is an inequality. Shapes are (N, Ci, H, Co, k, stride, pad).
 
-Out of scope (their math is not integer-closed): the fused BN-backward epilogue, the fp8 forward and dgrad.
+The fused epilogues (fused output, BN backward, the ``xbn`` operand) and the fp8 forward and dgrad are integer-closed
+too once the BatchNorm constants are dyadic: tests/test_epilogue_exact_gpu.py holds them to the same equality.
 Measured results and the kernels the default dispatch launched: profiles/exact_tests.md.
 """
 
