@@ -6,8 +6,8 @@
   (``csrc/comm``), linked against the ``librccl.so`` bundled with torch (the
   same library c10d's ProcessGroupNCCL uses).
 * ``_native/libimagent_runtime.so`` - host runtime (bucket planner / ready
-  tracker, record loader, the weight-gradient launchers' split planner,
-  ``csrc/runtime``), plain C++.
+  tracker, record loader, the weight-gradient launchers' split planner, the
+  forward / dgrad conv dispatch plan, ``csrc/runtime``), plain C++.
 
 All three expose a C ABI and are loaded with ctypes (``ops/_lib.py``), so they
 do not depend on the torch C++ ABI. A library is rebuilt when the SHA-256 of its
@@ -150,7 +150,9 @@ def build_comm(force: bool = False) -> str:
 
 def build_runtime(force: bool = False) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")))
-    hdrs = [os.path.join(CSRC, "kernels", "conv_wgrad_plan.h")]  # (wgrad_plan.cpp: the launchers' split planner)
+    # (wgrad_plan.cpp: the weight-gradient launchers' split planner; conv_plan.cpp: the forward / dgrad dispatch plan)
+    hdrs = [os.path.join(CSRC, "kernels", h)
+            for h in ("conv_wgrad_plan.h", "conv_plan.h", "conv_args.h", "conv_kernel_lists.h")]
     out = os.path.join(OUT, "libimagent_runtime.so")
     cxx = shutil.which("g++") or "c++"
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", out] + srcs

@@ -115,6 +115,18 @@ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
 extern "C" int g_imk_conv_launches;
 #define CONV_COUNTED() (++g_imk_conv_launches)
 
+// CUs of the current device (256, the MI355X's, where there is none to ask)
+inline int device_cus() {
+    static const int n = [] {
+        int dev = 0, cus = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            cus = 256;
+        return cus;
+    }();
+    return n;
+}
+
 #define IMK_CHECK_LAUNCH()                         \
     do {                                           \
         hipError_t e_ = hipGetLastError();         \

@@ -349,17 +349,6 @@ __global__ __launch_bounds__(512, 1) void halo3x3_kernel(const IGemmArgs a, int 
     }
 }
 
-int halo_cus() {
-    static const int n = [] {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        return cus;
-    }();
-    return n;
-}
-
 // blocks per CU: one persistent block per CU (2 measured within noise, round-4 switch sweep)
 constexpr int HALO_BLOCKS_PER_CU = 1;
 
@@ -367,35 +356,19 @@ template <int W, int R, int EPI>
 int launch_halo(const IGemmArgs& a, hipStream_t st) {
     const size_t lds = halo_lds(W, R);
     const int nbands = a.N * (a.H / R);
-    const int G = std::min(nbands, halo_cus() * HALO_BLOCKS_PER_CU);
+    const int G = std::min(nbands, device_cus() * HALO_BLOCKS_PER_CU);
     hipLaunchKernelGGL((halo3x3_kernel<W, R, EPI>), dim3(G), dim3(512), lds, st, a, nbands);
     CONV_COUNTED();
     IMK_CHECK_LAUNCH();
     return 0;
 }
 
-bool tap_in_halo(int d0, int ds) { return d0 >= -1 && d0 <= 1 && d0 + 2 * ds >= -1 && d0 + 2 * ds <= 1; }
-
 }  // namespace
 
-// Returns 1 when the shape / flags are not the halo kernel's (caller falls back).
-int conv_halo(const IGemmArgs& a, hipStream_t st) {
-    if (a.flags & (IG_OUT_F32 | IG_STEM | IG_REGSTAGE | IG_FP8 | IG_ACCUM_SUB2)) return 1;
-    // the eval forward's folded BatchNorm (+ ReLU after the optional accumulate): plain epilogue only
-    if ((a.flags & (IG_AFFINE | IG_RELU)) && ((a.flags & IG_BNBWD) || a.stats || a.xbn)) return 1;
-    if ((a.flags & IG_RELU) && !(a.flags & IG_AFFINE)) return 1;
-    if ((a.bias && !(a.flags & IG_AFFINE)) || a.C != 64 || a.Nout != 64 || a.ldb < 9 * 64 || a.ldy != 64) return 1;
-    if (a.nth != 3 || a.ntw != 3 || a.KW != 3 || a.sA != 1 || a.sY != 1 || a.oy != 0 || a.ox != 0) return 1;
-    if (a.OH != a.H || a.OW != a.W || a.YH != a.H || a.YW != a.W) return 1;
-    if (!tap_in_halo(a.dh0, a.dhs) || !tap_in_halo(a.dw0, a.dws)) return 1;
-    if (a.kh0 + 2 * a.khs < 0 || a.kh0 + 2 * a.khs > 2 || a.kh0 < 0 || a.kh0 > 2) return 1;
-    if (a.kw0 + 2 * a.kws < 0 || a.kw0 + 2 * a.kws > 2 || a.kw0 < 0 || a.kw0 > 2) return 1;
-    const bool bnb = a.flags & IG_BNBWD;
-    if (bnb && a.bnx2 && !a.bnym) return 1;  // a second BN branch needs the output's mask bits (c2/c3 hold its constants)
-    if (a.W == 56 && a.H % 4 == 0)
-        return bnb ? (a.bnx2 ? launch_halo<56, 4, 2>(a, st) : launch_halo<56, 4, 1>(a, st)) : launch_halo<56, 4, 0>(a, st);
-    if (a.W == 112 && a.H % 2 == 0)
-        return bnb ? (a.bnx2 ? launch_halo<112, 2, 2>(a, st) : launch_halo<112, 2, 1>(a, st))
-                   : launch_halo<112, 2, 0>(a, st);
-    return 1;
+// (which of them a conv runs: conv_plan.h, halo_plan)
+int conv_launch_halo(const ConvKernel& k, const IGemmArgs& a, hipStream_t st) {
+#define X(...) CONV_LAUNCH_IF(CONV_HALO, launch_halo, __VA_ARGS__)
+    CONV_HALO_KERNELS(X)
+#undef X
+    return CONV_RC_UNLISTED;
 }

@@ -413,24 +413,7 @@ int launch_v3(const IGemmArgs& a, hipStream_t st) {
     return 0;
 }
 
-// shapes v3 covers: C % 64 == 0 (one tap per stage), taps <= 32, operands < 2^31 bytes, and the staged
-// bf16 epilogue (no bias; ReLU only with the eval forward's folded BatchNorm, IG_AFFINE, without statistics)
-inline bool v3_ok(const IGemmArgs& a) {
-    if (a.C % 64 || a.nth * a.ntw > 32 || a.nth < 1 || a.ntw < 1) return false;
-    if (a.flags & (IG_OUT_F32 | IG_STEM | IG_FP8)) return false;
-    const bool eval_bn = a.flags & IG_AFFINE;
-    if ((a.flags & IG_RELU) && !eval_bn) return false;
-    if (eval_bn && (a.stats || (a.flags & IG_BNBWD))) return false;
-    const bool bnb_bias = (a.flags & IG_BNBWD) && a.X2;  // the second segment's bias (bn_gram.hip)
-    if ((a.bias && !eval_bn && !bnb_bias) || a.xbn || a.Nout % 8 || a.ldy % 8) return false;
-    if (a.X2 && (a.C2 % 64 || a.C2 <= 0 || a.nth != 1 || a.ntw != 1 || a.sA != 1 || a.H != a.OH || a.W != a.OW ||
-                 a.ldb < a.C + a.C2))
-        return false;
-    // (X / X2 descriptors are tile-based: any size; one image must stay below 2^31 bytes, the weights too)
-    const size_t ib = (size_t)a.H * a.W * a.C * 2 * 4, wb = (size_t)a.Nout * a.ldb * 2;
-    return ib < (1ull << 31) && wb < (1ull << 31);
-}
-
+// (the bf16 / fp8 shapes v3 covers: conv_plan.h, v3_ok / v3_ok8)
 // fp32 (3 x bf16 split, EB = 4) shapes v3 covers: C % 32 == 0 (one tap per 32-deep stage), fp32 out with
 // optional bias / accumulate, Nout and ldy % 4 == 0 (16-B stores)
 inline bool v3_ok32(const IGemmArgs& a) {
@@ -441,16 +424,6 @@ inline bool v3_ok32(const IGemmArgs& a) {
                                  (a.flags & IG_ACCUM)))
         return false;
     const size_t xb = (size_t)a.N * a.H * a.W * a.C * 4, wb = (size_t)a.Nout * a.ldb * 4;
-    return xb < (1ull << 31) && wb < (1ull << 31);
-}
-
-// fp8 shapes v3 covers (EB = 1): C % 128 == 0 (one tap per 128-deep stage), the staged bf16 epilogue
-// (statistics, fused BN backward, accumulate), no second K segment, scales present
-inline bool v3_ok8(const IGemmArgs& a) {
-    if (!(a.flags & IG_FP8) || a.C % 128 || a.nth * a.ntw > 32 || a.nth < 1 || a.ntw < 1) return false;
-    if (a.flags & (IG_OUT_F32 | IG_STEM | IG_RELU | IG_AFFINE | IG_EPI_DIRECT)) return false;
-    if (a.bias || a.xbn || a.X2 || !a.xexp || !a.wexp || a.Nout % 8 || a.ldy % 8) return false;
-    const size_t xb = (size_t)a.N * a.H * a.W * a.C, wb = (size_t)a.Nout * a.ldb;
     return xb < (1ull << 31) && wb < (1ull << 31);
 }
 

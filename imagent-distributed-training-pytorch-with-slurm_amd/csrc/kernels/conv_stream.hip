@@ -649,7 +649,7 @@ int launch_stream1(const IGemmArgs& a, hipStream_t st) {
         if (lds > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess)
-            return -123;
+            return CONV_RC_LAUNCH;
         resident = resident_blocks(kern, lds, NW * 64);
     }
     const int nsl = a.Nout / BN;
@@ -660,22 +660,6 @@ int launch_stream1(const IGemmArgs& a, hipStream_t st) {
     CONV_COUNTED();
     IMK_CHECK_LAUNCH();
     return 0;
-}
-
-template <int K, int BN, int D>
-int launch_plain(const IGemmArgs& a, hipStream_t st) {
-    if (a.flags & (IG_RES | IG_MASKOUT | IG_Q8OUT)) return launch_stream1<K, BN, D, 4>(a, st);
-    return launch_stream1<K, BN, D, 0>(a, st);
-}
-
-template <int K, int BN, int D>
-int launch_stream(const IGemmArgs& a, hipStream_t st) {
-    if (!(a.flags & IG_BNBWD)) return launch_plain<K, BN, D>(a, st);
-    if constexpr (BN <= 128) {
-        if (a.bnx2) return a.bnym ? launch_stream1<K, BN, D, 3>(a, st) : 1;
-        return a.bnym ? launch_stream1<K, BN, D, 1>(a, st) : launch_stream1<K, BN, D, 2>(a, st);
-    }
-    return 1;
 }
 
 // The 7x7 / stride-2 stem (C = 4 padded channels -> 64) as a band kernel: a persistent block stages R output rows'
@@ -843,20 +827,10 @@ __global__ __launch_bounds__(256, 2) void stem_band_kernel(const IGemmArgs a, in
     }
 }
 
-// the band stem's shapes: 4-channel 224-wide input, 7x7 / stride 2 / pad 3, 64 channels, 16 | OW, dense bf16 output
-bool stem_band_ok(const IGemmArgs& a) {
-    if (a.flags & (IG_OUT_F32 | IG_FP8 | IG_ACCUM | IG_BNBWD | IG_NOSTREAM | IG_RES | IG_MASKOUT | IG_Q8OUT)) return false;
-    if ((a.flags & IG_RELU) && !(a.flags & IG_AFFINE)) return false;
-    if ((a.bias && !(a.flags & IG_AFFINE)) || a.xbn || a.X2) return false;
-    return a.C == 4 && a.W == 224 && a.nth == 7 && a.ntw == 7 && a.sA == 2 && a.dh0 == -3 && a.dw0 == -3 &&
-           a.dhs == 1 && a.dws == 1 && a.Nout == 64 && a.ldb == 7 * 32 && a.ldy == 64 && a.OW % 16 == 0 &&
-           2 * (a.OW - 1) - 3 + 8 <= a.W + 3 && a.sY == 1 && a.YH == a.OH && a.YW == a.OW && a.oy == 0 && a.ox == 0;
-}
-
+template <int R>
 int launch_stem_band(const IGemmArgs& a, hipStream_t st) {
-    // R = 4 output rows per band (2048 img: 1,205 us; R = 2 1,391, R = 6 1,344 and R = 8 2,258 spill -- the 28 weight
-    // fragments held in registers leave no room for a taller band's prefetch)
-    constexpr int R = 4;
+    // (R = 4 output rows per band, conv_kernel_lists.h: 2048 img 1,205 us; R = 2 1,391, R = 6 1,344 and R = 8 2,258
+    // spill -- the 28 weight fragments held in registers leave no room for a taller band's prefetch)
     const size_t lds = 2 * (size_t)(2 * R + 5) * 232 * 8 + 4 * 16 * 64 * 2;
     static int resident = 0;
     if (resident == 0) resident = resident_blocks(stem_band_kernel<R>, lds);
@@ -869,129 +843,16 @@ int launch_stem_band(const IGemmArgs& a, hipStream_t st) {
 
 }  // namespace
 
-// the 7x7 stem forward: the band kernel (tile 0) or the streaming row-segment kernel (tile 23, A/B); 1: not covered
-int conv_stem(const IGemmArgs& a, hipStream_t st, int tile) {
-    if (tile == 0 && stem_band_ok(a)) return launch_stem_band(a, st);
-    return conv_stream(a, st, 0);
-}
-
-// Returns 1 if the shape is not one this kernel covers (caller falls back).
-// bn: channel-slice width (0 auto: the widest that divides Nout; 64/128/256 forced)
-int conv_stream(const IGemmArgs& a, hipStream_t st, int bn) {
-    const int bn_hint = bn;  // explicit slice width (tiles 20-22), before the defaults below
-    // the eval forward's folded BatchNorm (+ ReLU): plain epilogue, no statistics
-    const bool eval_bn = a.flags & IG_AFFINE;
-    if ((a.flags & IG_RELU) && !eval_bn) return 1;
-    if (eval_bn && (a.stats || a.xbn || (a.flags & IG_BNBWD))) return 1;
-    if ((a.flags & (IG_RES | IG_MASKOUT | IG_Q8OUT)) &&
-        (!eval_bn || (a.flags & (IG_ACCUM | IG_BNBWD | IG_STEM)) || ((a.flags & IG_RES) && !a.bnx) ||
-         ((a.flags & IG_MASKOUT) && (!a.bnym || !(a.flags & IG_RELU))) ||
-         ((a.flags & IG_Q8OUT) && (!a.Y8 || !a.y8exp || !a.y8amax))))
-        return -121;
-    // IG_NEXT1: the fused-output kernel's single-slice form only (K = 64 into 256 channels on the same pixels, no
-    // e4m3 copy), the next conv into 64 channels; anything else is an error, never another kernel
-    if (a.flags & IG_NEXT1) {
-        // (Co2 = 128, layer 1 into layer 2: a 64-KB W2 image and all 160 KB of a CU's LDS; built and measured, 1.2 ms
-        // less stand-alone but in-step within the noise, profiles/ab/next_conv1.txt: not kept)
-        if (!(a.flags & (IG_RES | IG_MASKOUT)) ||
-            (a.flags & (IG_Q8OUT | IG_OUT_F32 | IG_FP8 | IG_REGSTAGE | IG_NOSTREAM)) || a.stats || a.xbn || a.X2 ||
-            a.C != 64 || a.Nout != 256 || (bn != 0 && bn != 256) || !a.W2 || !a.Y2 || a.Co2 != 64 || a.ldb2 < 256 ||
-            a.ldb2 % 8 || a.nth != 1 || a.ntw != 1 || a.sA != 1 || a.H != a.OH || a.W != a.OW || a.dh0 != 0 ||
-            a.dw0 != 0 || a.kh0 != 0 || a.kw0 != 0 || a.sY != 1 || a.oy != 0 || a.ox != 0 || a.YH != a.OH ||
-            a.YW != a.OW || a.ldy != a.Nout || a.ldb < a.C)
-            return -122;
-        // D = 1 (2 spills 26 VGPRs); the next group's residual rows are then prefetched too (EPF), issued before
-        // the second GEMM
-        return launch_stream1<64, 256, 1, 5>(a, st);
+// (which of them a conv runs: conv_plan.h, stream_plan / stem_band_ok)
+int conv_launch_stream(const ConvKernel& k, const IGemmArgs& a, hipStream_t st) {
+    if (k.fam == CONV_STEM_BAND) {
+#define X(...) CONV_LAUNCH_IF(CONV_STEM_BAND, launch_stem_band, __VA_ARGS__)
+        CONV_STEM_BAND_KERNELS(X)
+#undef X
+    } else {
+#define X(...) CONV_LAUNCH_IF(CONV_STREAM, launch_stream1, __VA_ARGS__)
+        CONV_STREAM_KERNELS(X)
+#undef X
     }
-    const bool has_bias = a.bias && !eval_bn;
-    if (a.X2) {
-        // the Gram-form conv3 dgrad of a 64-channel bottleneck (bn_gram.hip): K = [g (256) | h2 (64)] into 64
-        // channels with bn2's BN-backward epilogue, weights [64][320] resident in LDS (the 128 x 64 v3 tile
-        // re-stages them per tile and ran these HBM streams at ~2.7 TB/s)
-        if (!(a.flags & IG_BNBWD) || (a.flags & (IG_ACCUM | IG_FP8 | IG_OUT_F32 | IG_AFFINE | IG_NOSTREAM | IG_RES |
-                                                  IG_MASKOUT | IG_Q8OUT)) ||
-            a.C != 256 || a.C2 != 64 || a.Nout != 64 || a.ldb != 320 || a.ldy != 64 || !a.bias || a.bnx2 ||
-            a.nth != 1 || a.ntw != 1 || a.sA != 1 || a.H != a.OH || a.W != a.OW || a.sY != 1 || a.YH != a.OH ||
-            a.YW != a.OW || a.dh0 != 0 || a.dw0 != 0 || a.kh0 != 0 || a.kw0 != 0 || a.oy != 0 || a.ox != 0)
-            return 1;
-        return a.bnym ? launch_stream1<256, 64, 2, 1, false, false, 64>(a, st)
-                      : launch_stream1<256, 64, 2, 2, false, false, 64>(a, st);
-    }
-    if (a.flags & IG_STEM) {  // 7x7 stem, C = 4, K = 7 x 32
-        if (a.flags & (IG_OUT_F32 | IG_FP8 | IG_ACCUM | IG_BNBWD | IG_NOSTREAM)) return 1;
-        if (has_bias || a.C != 4 || a.nth != 7 || a.ntw > 8 || a.ldb != 7 * 32 || a.Nout % 64 || a.ldy != a.Nout ||
-            a.sY != 1 || a.YH != a.OH || a.YW != a.OW)
-            return 1;
-        return launch_stream1<7 * 32, 64, 2, 0, true>(a, st);
-    }
-    if (a.flags & (IG_OUT_F32 | IG_FP8 | IG_REGSTAGE | IG_NOSTREAM)) return 1;
-    if (a.xbn) {  // BN apply + ReLU on the operand load: K = 64 / 128 plain-epilogue 1x1 convs only
-        if ((a.flags & (IG_BNBWD | IG_ACCUM)) || a.bias || a.nth != 1 || a.ntw != 1 || a.sA != 1 ||
-            a.H != a.OH || a.W != a.OW || a.sY != 1 || a.YH != a.OH || a.YW != a.OW || a.ldy != a.Nout ||
-            a.ldb < a.C || a.dh0 != 0 || a.dw0 != 0)
-            return -120;
-        if (a.C == 64 && a.Nout % 256 == 0) return launch_stream1<64, 256, 2, 0, false, true>(a, st);
-        if (a.C == 64 && a.Nout % 128 == 0) return launch_stream1<64, 128, 3, 0, false, true>(a, st);
-        if (a.C == 128 && a.Nout % 128 == 0) return launch_stream1<128, 128, 2, 0, false, true>(a, st);
-        return -120;
-    }
-    if (has_bias || a.nth != 1 || a.ntw != 1 || a.dh0 != 0 || a.dw0 != 0 || a.kh0 != 0 || a.kw0 != 0) return 1;
-    if (a.sY != 1 || a.oy != 0 || a.ox != 0 || a.YH != a.OH || a.YW != a.OW || a.ldy != a.Nout) return 1;
-    if (a.Nout % 64 != 0 || a.ldb < a.C) return 1;
-    if ((long)(a.OH - 1) * a.sA >= a.H || (long)(a.OW - 1) * a.sA >= a.W) return 1;
-    // K = 256 into > 128 channels (bottleneck conv3 / downsample forwards): 64-channel
-    // weight slices resident in LDS, the slices of one pixel range on one XCD (the pixels
-    // are fetched from HBM once and re-read from that XCD's L2).
-    // Only K = 256: at K = 512 the v3 tiles win (conv_bench at 1024 img: 512 -> 2048 @7 fwd 210 -> 179 us,
-    // 512 -> 1024 /2 @28 443 -> 375, 2048 -> 512 dgrad 209 -> 152; K = 256 stays here: 256 -> 1024 @14
-    // fwd 264 vs 370).
-    // 128-channel slices where Nout allows (half the slices re-reading each pixel group, twice the MFMAs per
-    // loaded fragment: 256 -> 1024 @14 fwd 277 -> 246 us at 1024 img, round 5); tile 22 forces 64
-    if (!(a.flags & IG_BNBWD) && a.C == 256 && a.Nout > 128) {
-        if (bn != 64 && a.Nout % 128 == 0) return launch_plain<256, 128, 2>(a, st);
-        if (bn != 0 && bn != 64) return 1;
-        return launch_plain<256, 64, 2>(a, st);
-    }
-    int maxbn = (a.C == 64 && !(a.flags & IG_BNBWD)) ? 256 : 128;
-    if (a.flags & IG_BNBWD) {
-        // BN-backward epilogue: every K = 64 / 128 / 256 dgrad, with or without the second BN branch, 128-channel
-        // slices. Same-box bench A/B at R50 / 1024 with the ReLU mask as bits (round 3): 73.9 ms/step vs 75.2 with
-        // K = 128 on the tiled kernels and 75.0 with the second branch there too; 64-channel slices neutral
-        maxbn = 128;
-    }
-    if (bn == 0) bn = maxbn;
-    while (bn > 64 && (bn > maxbn || a.Nout % bn)) bn >>= 1;
-    if (a.C == 64) {
-        // 256-channel slices: the fused-output / operand-BN variants prefetch 2 groups (3 spill at 256 VGPRs)
-        if (bn == 256)
-            return (a.flags & (IG_RES | IG_MASKOUT | IG_Q8OUT)) ? launch_stream1<64, 256, 2, 4>(a, st)
-                                                                : launch_stream1<64, 256, 3, 0>(a, st);
-        if (bn == 128) return launch_stream<64, 128, 3>(a, st);
-        return launch_stream<64, 64, 3>(a, st);
-    }
-    if (a.C == 128) {
-        if (bn == 128) return launch_stream<128, 128, 2>(a, st);
-        return launch_stream<128, 64, 2>(a, st);
-    }
-    // K = 256 BN-backward dgrads into wide outputs (bottleneck conv1 dgrads 256 -> 512 @28, 256 -> 1024 @14): 64-channel
-    // weight slices resident in LDS (as the K = 256 forwards) instead of the one-tile-per-block v3 loop, whose
-    // 4-stage main loop leaves these epilogue-heavy GEMMs latency-bound (-20 % per call, round 4)
-    if (a.C == 256 && (a.flags & IG_BNBWD) && a.Nout > 128) {
-        // 128-channel slices (half the slices re-reading each pixel group): in-step A/B at 2048 img 16,622 / 16,663
-        // vs 16,530 / 16,522 img/s with 64 (1024 -> 256 @14 dgrad + BN backward 705 -> 488 us, 512 -> 256 @28
-        // 1460 -> 1033; at 1024 img round 5 they had measured even); tile 22 forces 64. The second-BN-branch form
-        // stays on 64 (at 128 it spills 96 B: in-step 16,604 / 16,651 vs 16,662 / 16,653)
-        if (bn_hint != 64 && a.Nout % 128 == 0 && !a.bnx2)
-            return a.bnym ? launch_stream1<256, 128, 2, 1>(a, st) : launch_stream1<256, 128, 2, 2>(a, st);
-        if (a.bnx2) return a.bnym ? launch_stream1<256, 64, 2, 3>(a, st) : 1;
-        return a.bnym ? launch_stream1<256, 64, 2, 1>(a, st) : launch_stream1<256, 64, 2, 2>(a, st);
-    }
-    // K = 256 into <= 128 channels (bottleneck conv1 256 -> 64 / 128): 64-channel
-    // slices, plain epilogue
-    if (a.C == 256 && a.Nout <= 128) {
-        if (!(a.flags & IG_BNBWD)) return launch_plain<256, 64, 2>(a, st);
-        if (!a.bnx2) return a.bnym ? launch_stream1<256, 64, 2, 1>(a, st) : launch_stream1<256, 64, 2, 2>(a, st);
-    }
-    return 1;
+    return CONV_RC_UNLISTED;
 }

@@ -287,9 +287,24 @@ def _declare(name: str, lib) -> None:
         # the weight-gradient launchers' split-K plan (csrc/kernels/conv_wgrad_plan.h via csrc/runtime/wgrad_plan.cpp)
         lib.imr_wgrad_plan.argtypes = [i32, i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]
         lib.imr_wgrad_plan.restype = i32
+        # the forward / dgrad conv dispatch plan (csrc/kernels/conv_plan.h via csrc/runtime/conv_plan.cpp)
+        lib.imr_conv_plan.argtypes = [C.POINTER(IGemmArgs), i32, i32, i32, C.POINTER(C.c_int32)]
+        lib.imr_conv_plan.restype = i32
+        lib.imr_conv_tail_split_images.argtypes = [C.POINTER(IGemmArgs), i32]
+        lib.imr_conv_error_reason.argtypes = [i32]
+        lib.imr_conv_error_reason.restype = C.c_char_p
+        lib.imr_conv_flag.argtypes = [i32, C.c_char_p]
+        if lib.imr_conv_args_size() != C.sizeof(IGemmArgs):
+            raise RuntimeError(f"imr_conv_args_size: native {lib.imr_conv_args_size()} B != ctypes "
+                               f"{C.sizeof(IGemmArgs)} B - rebuild")
 
 
-STAT_SLOTS = 32  # conv epilogue statistics slab depth (csrc/kernels/conv_igemm.hip)
+STAT_SLOTS = 32  # conv epilogue statistics slab depth (csrc/kernels/conv_args.h)
+
+# IGemmArgs.flags (csrc/kernels/conv_args.h, where each is described; tests/test_conv_plan.py holds them to the header)
+IG_OUT_F32, IG_RELU, IG_STEM, IG_ACCUM, IG_REGSTAGE, IG_BNBWD, IG_EPI_LDS, IG_EPI_DIRECT = (1 << i for i in range(8))
+IG_FP8, IG_BF8X, IG_AFFINE, IG_NOSTREAM, IG_ACCUM_SUB2, IG_RES, IG_MASKOUT, IG_Q8OUT, IG_NEXT1 = \
+    (1 << i for i in range(8, 17))
 
 
 def ptr(t) -> int:
@@ -313,3 +328,11 @@ def zero_(t) -> None:
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise RuntimeError(f"{what} failed with code {rc}")
+
+
+def check_conv(rc: int, what: str) -> None:
+    """check() for imk_conv_igemm with the code's reason (csrc/kernels/conv_plan.h). The message still ends with
+    ``failed with code -NNN``: callers and tests match on that tail."""
+    if rc != 0:
+        why = runtime().imr_conv_error_reason(rc).decode() if available("runtime") else ""
+        raise RuntimeError(f"{what} ({why}) failed with code {rc}" if why else f"{what} failed with code {rc}")

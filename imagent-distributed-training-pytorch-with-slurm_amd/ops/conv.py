@@ -45,12 +45,12 @@ _log_file = None
 def _igemm_call(a, tile: int, st, what: str) -> None:
     k = _lib.kernels()
     if _LOG_PATH is None:
-        _lib.check(k.imk_conv_igemm(C.byref(a), tile, st), what)
+        _lib.check_conv(k.imk_conv_igemm(C.byref(a), tile, st), what)
         return
     n0 = k.imk_conv_launches()
-    _lib.check(k.imk_conv_igemm(C.byref(a), tile, st), what)
+    _lib.check_conv(k.imk_conv_igemm(C.byref(a), tile, st), what)
     _log(dict(op=what, N=a.N, H=a.H, W=a.W, C=a.C, OH=a.OH, OW=a.OW, M=a.M, Nout=a.Nout, taps=a.nth * a.ntw,
-              YH=a.YH, YW=a.YW, sY=a.sY, ldy=a.ldy, flags=a.flags, bnb=bool(a.flags & 32), y2=bool(a.bnym),
+              YH=a.YH, YW=a.YW, sY=a.sY, ldy=a.ldy, flags=a.flags, bnb=bool(a.flags & _lib.IG_BNBWD), y2=bool(a.bnym),
               x2=bool(a.bnx2), stats=bool(a.stats), xbn=bool(a.xbn), X2=bool(a.X2)),
          k.imk_conv_launches() - n0, st)
 
@@ -90,10 +90,10 @@ def _base_args(x_ptr, w_ptr, y_ptr, N, H, W, Cin, OH, OW, Nout, ldb, sA) -> _lib
 
 # epilogue choice: 0 auto (LDS-staged for fused BN backward, else direct),
 # 1 direct register epilogue, 2 LDS-staged coalesced epilogue
-_EPI_FLAGS = {0: 0, 1: 128, 2: 64}
+_EPI_FLAGS = {0: 0, 1: _lib.IG_EPI_DIRECT, 2: _lib.IG_EPI_LDS}
 # IMAGENT_CONV_STREAM=0: keep short-K 1x1 convs off the streaming kernel
 # (conv_stream.hip) -- A/B switch for benchmarks and numerics tests
-_NOSTREAM = 2048 if os.environ.get("IMAGENT_CONV_STREAM", "1") == "0" else 0
+_NOSTREAM = _lib.IG_NOSTREAM if os.environ.get("IMAGENT_CONV_STREAM", "1") == "0" else 0
 # IMAGENT_BN_SHIFT=0: forward BN statistics as raw sums (shift 0) -- A/B switch
 _SHIFT = os.environ.get("IMAGENT_BN_SHIFT", "1") != "0"
 
@@ -101,7 +101,7 @@ _SHIFT = os.environ.get("IMAGENT_BN_SHIFT", "1") != "0"
 def set_stream(enabled: bool) -> None:
     """Route short-K (C in {64, 128}) 1x1 convs to the streaming kernel or not."""
     global _NOSTREAM
-    _NOSTREAM = 0 if enabled else 2048
+    _NOSTREAM = 0 if enabled else _lib.IG_NOSTREAM
 
 
 # Deterministic mode (IMAGENT_DETERMINISTIC=1 or set_deterministic(True); bench / CLI --deterministic): BatchNorm
@@ -181,15 +181,15 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
     a.nth, a.ntw, a.dh0, a.dhs, a.dw0, a.dws = KH, KW, -pad, 1, -pad, 1
     a.kh0, a.khs, a.kw0, a.kws, a.KW = 0, 1, 0, 1, KW
     a.YH, a.YW, a.sY, a.oy, a.ox, a.ldy = OH, OW, 1, 0, 0, Co
-    a.flags = (1 if out_f32 else 0) | (2 if relu else 0) | (4 if stem else 0) | _EPI_FLAGS[epi] | \
-        (8 if accumulate else 0) | _NOSTREAM
+    a.flags = (_lib.IG_OUT_F32 if out_f32 else 0) | (_lib.IG_RELU if relu else 0) | (_lib.IG_STEM if stem else 0) | \
+        _EPI_FLAGS[epi] | (_lib.IG_ACCUM if accumulate else 0) | _NOSTREAM
     if affine is not None:
         assert bias is None and affine.shape == (2, Co) and affine.dtype == torch.float32
-        a.flags |= 1024
+        a.flags |= _lib.IG_AFFINE
         a.bias = affine.data_ptr()
     if res is not None:
         assert res.shape == out.shape and res.dtype == torch.bfloat16 and res.is_contiguous()
-        a.flags |= 8192
+        a.flags |= _lib.IG_RES
         a.bnx = res.data_ptr()
         if res_scale is not None:
             assert res_scale.dtype == torch.float32 and res_scale.numel() == Co and res_scale.is_contiguous()
@@ -197,15 +197,15 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
     if q8out is not None:
         y8, e8, a8 = q8out
         assert y8.dtype == torch.uint8 and y8.numel() == out.numel() and e8.dtype == torch.int32
-        a.flags |= 32768
+        a.flags |= _lib.IG_Q8OUT
         a.Y8, a.y8exp, a.y8amax = y8.data_ptr(), e8.data_ptr(), a8.data_ptr()
     if maskout is not None:
         assert maskout.dtype == torch.uint8 and maskout.numel() * 8 == out.numel() and relu
-        a.flags |= 16384
+        a.flags |= _lib.IG_MASKOUT
         a.bnym = maskout.data_ptr()
     if fp8 is not None:
         assert x.dtype == torch.uint8 and w.dtype == torch.uint8, (x.dtype, w.dtype)
-        a.flags |= 256
+        a.flags |= _lib.IG_FP8
         a.xexp, a.wexp = fp8[0].data_ptr(), fp8[1].data_ptr()
     if bias is not None:
         a.bias = bias.data_ptr()
@@ -218,7 +218,7 @@ def igemm_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, pad: int, KH: int, 
         assert w2.dtype == torch.bfloat16 and w2.is_contiguous() and w2.numel() == w2.shape[0] * Co and stats is None
         assert not _DET, "next1: statistics from the epilogue's atomics only"
         y2 = torch.empty((N, OH, OW, w2.shape[0]), device=x.device, dtype=torch.bfloat16)
-        a.flags |= 65536
+        a.flags |= _lib.IG_NEXT1
         a.W2, a.Y2, a.Co2, a.ldb2 = w2.data_ptr(), y2.data_ptr(), w2.shape[0], Co
         if st2 is not None:
             if hasattr(st2, "slab"):  # a BatchNorm's workspace, as ``stats`` below
@@ -315,8 +315,9 @@ def igemm_dgrad(dy: torch.Tensor, wt: torch.Tensor, in_hw: Tuple[int, int], stri
             a.dw0, a.dws = (pw + pad - kw0) // S, -1
             a.kh0, a.khs, a.kw0, a.kws, a.KW = kh0, S, kw0, S, KW
             a.YH, a.YW, a.sY, a.oy, a.ox, a.ldy = H, W, S, ph, pw, Ci
-            a.flags = (8 if accumulate else 0) | _EPI_FLAGS[epi] | (256 | 512 if fp8 is not None else 0) | _NOSTREAM | \
-                (4096 if (accumulate and old_sub2) else 0)
+            a.flags = (_lib.IG_ACCUM if accumulate else 0) | _EPI_FLAGS[epi] | _NOSTREAM | \
+                (_lib.IG_FP8 | _lib.IG_BF8X if fp8 is not None else 0) | \
+                (_lib.IG_ACCUM_SUB2 if (accumulate and old_sub2) else 0)
             if bnb is not None:
                 bnb.fill(a)
             _igemm_call(a, tile, st, "conv dgrad")
@@ -337,7 +338,7 @@ class BNBwdFuse:
 
     def fill(self, a) -> None:
         w = self.bn.work
-        a.flags |= 32
+        a.flags |= _lib.IG_BNBWD
         a.stats = w.scratch.data_ptr()
         # x None (with the mask bits): the epilogue never reads x; sum(g xhat) is then formed from g^T h2 by the
         # Gram-form bn3 backward (ops/bn_gram.py gram_coef with T)
