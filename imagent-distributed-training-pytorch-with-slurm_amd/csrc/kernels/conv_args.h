@@ -63,6 +63,14 @@ struct IGemmArgs {
     float* stats2;
     const float* shift2;
     int Co2, ldb2;
+    // gt_T non-null (streaming 1x1 only; IG_BNBWD from the mask bits without x, with IG_ACCUM -- a bottleneck's conv1
+    // dgrad finishing the PREVIOUS Gram-form block's output gradient g): the same launch also accumulates
+    // gt_T [Nout][gt_p] fp32 += g^T h2 over the stored bf16 bits of g, with gt_h2 [M][gt_p] bf16 that block's conv3
+    // input (bn_gram.hip's T, the pass ops/bn_gram.py gram_T otherwise makes over g). A request, not a hint: a shape
+    // the kernel does not cover is an error (conv_plan.h -125). Signalled by the pointer, as xbn / X2 are
+    const bf16_t* gt_h2;
+    float* gt_T;
+    int gt_p;
 };
 
 #define IG_OUT_F32 1   // fp32 output (else bf16)

@@ -45,7 +45,8 @@
 
 // conv_stream_kernel<K, BN, D, MODE, STEM, XBN, K2> (conv_stream.hip): the 256-channel slice of K = 64 with the next
 // conv1 (mode 5), the two-segment Gram dgrads, the row-segment stem, the operand-BN forms, then the slice kernels:
-// fused-output (4) and plain (0), BN backward with a second branch (3), from the mask bits (1), from x (2)
+// fused-output (4) and plain (0), BN backward with a second branch (3), from the mask bits (1), from x (2); last the
+// mask-bit dgrads that also form the previous Gram-form block's T = g^T h2 (6 = 1 + T, 7 = 3 + T; p = 64)
 #define CONV_STREAM_PLAIN_(X, K, BN, D) X(K, BN, D, 4, false, false, 0) X(K, BN, D, 0, false, false, 0)
 #define CONV_STREAM_BNB_(X, K, BN, D) X(K, BN, D, 1, false, false, 0) X(K, BN, D, 2, false, false, 0)
 #define CONV_STREAM_ALL_(X, K, BN, D)                                                                         \
@@ -58,7 +59,8 @@
     X(64, 256, 2, 4, false, false, 0) X(64, 256, 3, 0, false, false, 0)                                       \
     CONV_STREAM_ALL_(X, 64, 128, 3) CONV_STREAM_ALL_(X, 64, 64, 3) CONV_STREAM_ALL_(X, 128, 128, 2)           \
     CONV_STREAM_ALL_(X, 128, 64, 2)                                                                           \
-    CONV_STREAM_BNB_(X, 256, 128, 2) X(256, 64, 2, 3, false, false, 0) CONV_STREAM_BNB_(X, 256, 64, 2)
+    CONV_STREAM_BNB_(X, 256, 128, 2) X(256, 64, 2, 3, false, false, 0) CONV_STREAM_BNB_(X, 256, 64, 2)         \
+    X(64, 128, 3, 6, false, false, 0) X(64, 128, 3, 7, false, false, 0) X(128, 128, 2, 6, false, false, 0)
 
 // stem_band_kernel<R> (conv_stream.hip)
 #define CONV_STEM_BAND_KERNELS(X) X(4)

@@ -99,6 +99,8 @@ inline const char* conv_error_reason(int rc) {
         case -120: return "the operand BatchNorm (xbn): only the 64 -> 64 3x3 halo kernel and the K = 64 / 128 streaming 1x1";
         case -121: return "IG_RES / IG_MASKOUT / IG_Q8OUT / IG_NEXT1: only the streaming 1x1 kernel has that epilogue";
         case -122: return "IG_NEXT1: only the 64 -> 256 single-slice fused-output form into 64 channels, tile 0";
+        case -125: return "gt_T (T = g^T h2 from the dgrad's epilogue): only the accumulating mask-bit BN-backward 1x1 dgrad "
+                          "without x on the streaming kernel, K = 64 / 128 into 256 channels, p = 64, tile 0";
         case CONV_RC_LAUNCH: return "setting the kernel's dynamic LDS size failed";
         case CONV_RC_UNLISTED: return "the planned kernel is not instantiated (conv_kernel_lists.h)";
     }
@@ -361,6 +363,24 @@ inline bool stream_plan(const IGemmArgs& a, int bn, ConvPlan& p) {
     return false;
 }
 
+// ---- the streaming BN-backward dgrad that also forms T = g^T h2 (conv_args.h gt_T; conv_stream.hip modes 6 / 7): the
+// next block's conv1 dgrad, K = 64 / 128 into the 4p = 256 channels of a p = 64 bottleneck (ResNet-50's layer 1 and
+// the first block of layer 2), mask bits without x, accumulating. Anything else with gt_T set is the error -125,
+// never a kernel that would ignore T
+// (p = 128, K = 128 / 256 into 512: not built; p = 256: the K = 256 producers have no registers left)
+inline ConvPlan gramt_plan(const IGemmArgs& a, int tile) {
+    constexpr int need = IG_BNBWD | IG_ACCUM;
+    constexpr int never = IG_OUT_F32 | IG_RELU | IG_STEM | IG_REGSTAGE | IG_EPI_DIRECT | IG_FP8 | IG_BF8X | IG_AFFINE |
+                          IG_NOSTREAM | IG_FUSED_OUT | IG_NEXT1;
+    if (tile != 0 || (a.flags & need) != need || (a.flags & never) || a.bnx || !a.bnym || !a.gt_h2 || a.gt_p != 64 ||
+        a.Nout != 4 * a.gt_p || (a.C != 64 && a.C != 128) || (a.C == 128 && a.bnx2) || a.bias || a.xbn || a.X2 ||
+        a.nth != 1 || a.ntw != 1 || a.sA != 1 || a.H != a.OH || a.W != a.OW || a.dh0 != 0 || a.dw0 != 0 ||
+        a.kh0 != 0 || a.kw0 != 0 || a.sY != 1 || a.oy != 0 || a.ox != 0 || a.YH != a.OH || a.YW != a.OW ||
+        a.ldy != a.Nout || a.ldb < a.C)
+        return fail(-125);
+    return one(a, a.C == 64 ? stream(64, 128, 3, a.bnx2 ? 7 : 6) : stream(128, 128, 2, 6));
+}
+
 // ---- fp8 (conv_igemm_fp8.hip): C % 128 == 0 (every ResNet conv but the 64-channel ones of the first stage) runs the
 // v3 LDS-DMA main loop with 1-byte operands (conv_igemm_v3.h, EB = 1): 256x256 tiles for Nout >= 512 with enough
 // tiles and K >= 512, 128x128 for Nout >= 128, 128x64 below; explicit tiles 17 / 18 / 19 force those.
@@ -442,6 +462,7 @@ inline ConvPlan conv_plan(const IGemmArgs& a, int tile, int cus, bool v3_deep) {
                                  (a.bnx2 && !a.bnsave2)))
         return fail(-104);
     if ((a.flags & IG_NEXT1) && ((a.flags & IG_STEM) || a.xbn || a.X2 || tile != 0)) return fail(-122);
+    if (a.gt_T) return gramt_plan(a, tile);
     ConvPlan p;
     ConvKernel k;
     if (a.flags & IG_STEM) {  // C == 4 row-segment gather, K = KH x 32

@@ -70,8 +70,28 @@ constexpr int stream_rp() {  // LDS weight row pitch in 16-B chunks: 16-chunk sw
 // accumulator on the stored bf16 bits, as conv_stream_kernel<256, 64, 2, 0> does on `out`: Y2 is bit-identical to
 // the stand-alone conv
 // (the template's parameter list stays as it was: the kernel names are what profiles and tests know them by)
-constexpr int stream_nw(int mode) { return mode == 5 ? 8 : 4; }    // waves per block
+//
+// MODES 6 / 7 (IGemmArgs::gt_T): MODE 1 / 3 (mask bits, no x, IG_ACCUM) whose block also accumulates the PREVIOUS
+// Gram-form bottleneck's T [Nout][P] += g^T h2 (bn_gram.hip) from the tiles of g it has just stored: g is written,
+// final, by this kernel alone, and a separate pass read all of it back a few microseconds later. The stored bits of
+// a group go into a second wave-private LDS tile (sG, 256-B rows in the image (b) of cdna_hip_programming.md T10,
+// conv_wgrad_v3.h's wg3_swz) next to the group's 16 rows of h2 (sH, buffer-loaded beside the epilogue operands with
+// the same out-of-range scheme: rows past M and groups past the end are zeros). Pixels are the MFMA k index of both
+// operands, so both are read with the transposing LDS read. A wave-private [128][64] fp32 accumulator does not fit
+// (128 registers); instead NW = 8 waves (one block per CU, as MODE 5) each own 128 / 8 = 16 channels x P of the
+// slice's T rows (16 registers) and every wave consumes all eight tiles once per round: 128 pixels = 4 k-steps x 4
+// fragments = 16 MFMAs per wave and round, as many as the conv itself at K = 64. Two block barriers per round (tiles
+// written -> read; read -> next round's writes, which sits after the next group's MFMAs), so every wave of a block
+// runs the same number of rounds (groups past the end are all out of range). T leaves once, one atomic per element
+// and block. dX, the mask handling and the slab sums are those of modes 1 / 3 bit for bit
+constexpr int stream_nw(int mode) { return mode >= 5 ? 8 : 4; }    // waves per block
 constexpr int stream_co2(int mode) { return mode == 5 ? 64 : 0; }  // the next conv's output channels
+constexpr int stream_gtp(int mode) { return mode >= 6 ? 64 : 0; }  // P of the T modes (the previous block's width)
+// h2 tile [16][64] bf16, 128-B rows: 32-B slot s of row r at s ^ gsw(r). A 32-lane half of a transposing read takes
+// rows {0..3, 8..11} or {4..7, 12..15} of one 32-B column window: the four rows of either parity then fall into four
+// different windows, the two parities into the two halves of the 256-B bank line -- conflict-free
+__device__ __forceinline__ int gt_hswz(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
+__device__ __forceinline__ int gt_gswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }  // image (b), 16-B chunks
 
 template <int K, int BN, int D, int MODE, bool STEM = false, bool XBN = false, int K2 = 0>
 __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(const IGemmArgs a) {
@@ -87,8 +107,12 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
     constexpr int CH = BN / 8;        // 16-B output chunks per pixel
     constexpr int PPR = 64 / CH;      // pixels per epilogue read instruction
     constexpr int NR = 16 / PPR;      // epilogue reads per 16-pixel group
-    constexpr bool bnb = MODE >= 1 && MODE <= 3, has_y = MODE == 1 || MODE == 3, has_x2 = MODE == 3;
+    constexpr bool GT = MODE == 6 || MODE == 7;         // + T = g^T h2 (above)
+    constexpr int EM = MODE == 6 ? 1 : MODE == 7 ? 3 : MODE;  // the epilogue's mode
+    constexpr int P = stream_gtp(MODE);
+    constexpr bool bnb = EM >= 1 && EM <= 3, has_y = EM == 1 || EM == 3, has_x2 = EM == 3;
     constexpr bool FO = MODE == 4 || MODE == 5, NX = MODE == 5;
+    static_assert(!GT || (BN == 128 && P == 64 && K2 == 0 && !STEM && !XBN), "T modes: 128-channel slices, p = 64");
     constexpr int RB2 = BN * 2;        // W2 row pitch in LDS (bytes): BN / 8 chunks, swizzled in groups of 16
     constexpr int FN2 = CO2 / 16;      // channel fragments of the second output
     constexpr int EP2 = CO2 * 2, CH2 = NX ? CO2 / 8 : 1, PPR2 = 64 / CH2, NR2 = NX ? 16 / PPR2 : 0;
@@ -103,6 +127,9 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
     char* sW = smem;
     char* sW2 = smem + BN * RB;  // (NX) the next conv's weights [CO2][BN]
     char* sE = smem + BN * RB + CO2 * RB2 + wid * 16 * EP;
+    // (GT) every wave's stored tile of g [16][BN] and its rows of h2 [16][P], read by all waves of the block
+    char* sG = smem + BN * RB + CO2 * RB2 + NW * 16 * EP;
+    char* sH = sG + NW * 16 * EP;
 
     const int nsl = a.Nout / BN;
     const int G = gridDim.x;  // multiple of nsl (host)
@@ -339,7 +366,20 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
             }
     }
 
-    for (int g0 = w0; g0 < ngroups; g0 += D * wstride) {
+    // (GT) T accumulators: rows n0 + wid * 16 + fq * 4 + i, columns jf * 16 + fr
+    f32x4 tacc[GT ? P / 16 : 1];
+#pragma unroll
+    for (int jf = 0; jf < (GT ? P / 16 : 1); ++jf) tacc[jf] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // ... and the transposing reads' addresses (as conv_wgrad_v3.h): MFMA k-step s covers the tiles of waves 2 s
+    // (k 0..3 of each lane) and 2 s + 1 (k 4..7); lane group tg takes rows trow .. of both (a 32-lane half's two
+    // blocks 8 rows apart), 8 B at columns 4 tp .. + 3 of this wave's 16 channels / of h2 column fragment jf
+    const int tg = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+    const int trow = (tg & 1) * 8 + (tg >> 1) * 4 + tq;
+    const int goff = trow * EP + (((wid * 2 + (tp >> 1)) ^ gt_gswz(trow)) << 4) + 8 * (tp & 1);
+    const int hoff = trow * 2 * P + (gt_hswz(trow) << 5) + 8 * tp;  // fragment jf: ^ (jf << 5), the slot swizzle
+
+    // (GT: the block's waves run the same rounds -- the loop holds block barriers)
+    for (int g0 = w0; (GT ? g0 - wid : g0) < ngroups; g0 += D * wstride) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const int g = g0 + d * wstride;  // past the end: every access out of range (no divergent exit)
@@ -370,7 +410,9 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
             auto issue = [&](int u) {  // late / at-group-start form of the epilogue operand loads
                 if (early || accum) oo[u] = buf_ld16(eb.ro, oo_off(g, u, o2[u]));
                 if (bnb) {
-                    xo[u] = buf_ld16(eb.rbx, o2[u]);
+                    // (GT: x is absent by the plan's conditions -- no load of it, and sum(g xhat), which T replaces,
+                    // is not formed: row 0 of the slab is left alone)
+                    if constexpr (!GT) xo[u] = buf_ld16(eb.rbx, o2[u]);
                     if (has_y) yo[u] = __builtin_amdgcn_raw_buffer_load_b8(eb.rym, ev[u] ? o2[u] >> 4 : BUF_OOB, 0, 0);
                     if (has_x2) x2o[u] = buf_ld16(eb.rx2o, o2[u]);
                 }
@@ -391,6 +433,18 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
 #pragma unroll
                 for (int u = 0; u < NR; ++u) issue(u);
             }
+            // (GT) the group's h2 rows, two 16-B chunks per lane (row j * 8 + lane / 8, chunk lane % 8): issued with
+            // the epilogue operands, before the next prefetch, unconditional as they are
+            u32x4 h2r[GT ? 2 : 1];
+            if constexpr (GT) {
+                const __amdgpu_buffer_rsrc_t rh = buf_rsrc(a.gt_h2 + (size_t)(g < ngroups ? g * 16 : 0) * P, true);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int hr = j * 8 + (lane >> 3);
+                    const bool hv = g < ngroups && g * 16 + hr < a.M;
+                    h2r[j] = buf_ld16(rh, hv ? (uint32_t)(hr * P * 2 + (lane & 7) * 16) : BUF_OOB);
+                }
+            }
             fetch(d, g + D * wstride);
             f32x4 acc[FN];
 #pragma unroll
@@ -398,7 +452,7 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
             // weight fragments through a ring of RR registers, read RR - 1 MFMAs ahead of use, MFMA t = (k-step
             // t / FN, channel fragment t % FN) (the group barriers pin the interleave: left to itself the scheduler
             // issued each ds_read right before its MFMA and waited for it, a full LDS latency per MFMA)
-            constexpr int NT = KS * FN, RR = NT < 8 ? NT : FN >= 16 && (FO || XBN) ? 3 : (FN >= 16 || MODE == 3 ? 4 : 8);
+            constexpr int NT = KS * FN, RR = NT < 8 ? NT : FN >= 16 && (FO || XBN) ? 3 : (FN >= 16 || EM == 3 ? 4 : 8);
             bf16x8 fa[RR];
 #pragma unroll
             for (int t = 0; t < RR - 1; ++t)
@@ -423,6 +477,8 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
                 *reinterpret_cast<u32x2*>(sE + fr * EP + epi_swz(fr, (i * 16 + fq * 4) * 2)) =
                     u32x2{pack_bf2(acc[i][0], acc[i][1]), pack_bf2(acc[i][2], acc[i][3])};
             __builtin_amdgcn_wave_barrier();
+            // (GT) every wave has read the previous round's sG / sH tiles: they may be written again
+            if constexpr (GT) __syncthreads();
             // (2) coalesced row chunks: pixel q*PPR + lane/CH, channels n .. n+7
 #pragma unroll
             for (int q0 = 0; q0 < NR; q0 += QB) {
@@ -465,8 +521,8 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
                     if (bnb) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            xv[2 * k] = lo_bf(xo[q][k]);
-                            xv[2 * k + 1] = hi_bf(xo[q][k]);
+                            xv[2 * k] = GT ? 0.f : lo_bf(xo[q][k]);
+                            xv[2 * k + 1] = GT ? 0.f : hi_bf(xo[q][k]);
                         }
 #pragma unroll
                         for (int c = 0; c < 8; ++c) {
@@ -479,6 +535,9 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
                     for (int k = 0; k < 4; ++k) o[k] = pack_bf2(v[2 * k], v[2 * k + 1]);
                     __builtin_amdgcn_raw_buffer_store_b128(o, eb.ry, o2[q], 0, 0);
                     if constexpr (NX) epi_write(sE, p, EP, cc, o);  // the stored bits: the next conv's pixel operand
+                    if constexpr (GT)  // the stored bits (rows past M: zeros), chunk cc of row p in image (b)
+                        *reinterpret_cast<u32x4*>(sG + wid * 16 * EP + p * EP + ((cc ^ gt_gswz(p)) << 4)) =
+                            ev[q] ? o : u32x4{0u, 0u, 0u, 0u};
                     if (q8out) {  // quantise the bf16-rounded values the bf16 consumers see
                         float w[8];
 #pragma unroll
@@ -511,7 +570,7 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
                         if (bnb) {
 #pragma unroll
                             for (int c = 0; c < 8; ++c) {
-                                s1[c] += v[c] * ((xv[c] - mean[c]) * rstd[c]);
+                                if constexpr (!GT) s1[c] += v[c] * ((xv[c] - mean[c]) * rstd[c]);
                                 s2[c] += v[c];
                             }
                             if (has_x2) {
@@ -591,7 +650,35 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
                 __builtin_amdgcn_wave_barrier();
             }
             if constexpr (EPF && !NX) issue_early(d, g + D * wstride);
+            if constexpr (GT) {
+                static_assert(!GT || !EPF, "T modes: the epilogue operands are issued at the group's start");
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int hr = j * 8 + (lane >> 3);
+                    *reinterpret_cast<u32x4*>(sH + wid * 16 * 2 * P + hr * 2 * P +
+                                              (((lane & 7) * 16) ^ (gt_hswz(hr) << 5))) = h2r[j];
+                }
+                __syncthreads();  // the round's NW tiles of g and h2 are complete
+                // T rows of this wave += (g tiles)^T (h2 tiles): EXEC is full here (no divergent path in the loop)
+#pragma unroll
+                for (int s = 0; s < NW / 2; ++s) {
+                    const char* gs = sG + 2 * s * 16 * EP;
+                    const char* hs = sH + 2 * s * 16 * 2 * P;
+                    const bf16x8 fg = tr16_frag(gs, goff, goff + 16 * EP);
+#pragma unroll
+                    for (int jf = 0; jf < P / 16; ++jf)
+                        tacc[jf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                            fg, tr16_frag(hs, hoff ^ (jf << 5), (hoff ^ (jf << 5)) + 16 * 2 * P), tacc[jf], 0, 0, 0);
+                }
+            }
         }
+    }
+    if constexpr (GT) {  // one atomic per T element and block: the waves own disjoint rows
+        float* tp0 = a.gt_T + (size_t)(n0 + wid * 16 + fq * 4) * P + fr;
+#pragma unroll
+        for (int jf = 0; jf < P / 16; ++jf)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) atomicAdd(tp0 + i * P + jf * 16, tacc[jf][i]);
     }
     if (q8out) {  // one atomic per wave into the 32-slot amax row
         m8 = wave_max(m8);
@@ -631,7 +718,7 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
     float* st = a.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * (bnb ? 3 : 2) * a.Nout;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        atomicAdd(st + n + c, s1[c]);
+        if constexpr (!GT) atomicAdd(st + n + c, s1[c]);
         atomicAdd(st + a.Nout + n + c, s2[c]);
         if (has_x2) atomicAdd(st + 2 * a.Nout + n + c, s3[c]);
     }
@@ -642,7 +729,11 @@ int launch_stream1(const IGemmArgs& a, hipStream_t st) {
     constexpr int NW = stream_nw(MODE), CO2 = stream_co2(MODE);
     constexpr int RP = stream_rp<STEM, K + K2>();
     // weight slice (+ the next conv's [CO2][BN] image) + one 16-pixel epilogue tile per wave
-    const size_t lds = (size_t)BN * RP * 16 + (size_t)CO2 * BN * 2 + NW * 16 * (BN * 2);
+    // (+ with T: the stored tile of g and the h2 rows of every wave)
+    constexpr int GP = stream_gtp(MODE);
+    const size_t lds = (size_t)BN * RP * 16 + (size_t)CO2 * BN * 2 + NW * 16 * (BN * 2) +
+                       (GP ? NW * 16 * (BN * 2 + GP * 2) : 0);
+    if (GP && (!a.gt_T || !a.gt_h2 || a.gt_p != GP)) return CONV_RC_UNLISTED;  // (the plan's conditions)
     const auto kern = conv_stream_kernel<K, BN, D, MODE, STEM, XBN, K2>;
     static int resident = 0;
     if (resident == 0) {

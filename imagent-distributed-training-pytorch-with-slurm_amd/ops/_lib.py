@@ -94,6 +94,7 @@ class IGemmArgs(C.Structure):
         ("Y8", C.c_void_p), ("y8exp", C.c_void_p), ("y8amax", C.c_void_p),
         ("W2", C.c_void_p), ("Y2", C.c_void_p), ("stats2", C.c_void_p), ("shift2", C.c_void_p),
         ("Co2", C.c_int), ("ldb2", C.c_int),
+        ("gt_h2", C.c_void_p), ("gt_T", C.c_void_p), ("gt_p", C.c_int),
     ]
 
 

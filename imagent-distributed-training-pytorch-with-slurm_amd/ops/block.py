@@ -87,6 +87,38 @@ _GRAM_FWD = os.environ.get("IMAGENT_BN_GRAM_FWD", "1") != "0"
 # BatchNorm statistics from the tile it has just stored (conv_stream.hip IG_NEXT1), bit-identical to the conv run
 # on the output: the next block's forward takes that result instead of reading the block output back from HBM
 _NEXT1 = os.environ.get("IMAGENT_NEXT_CONV1", "1") != "0"
+# IMAGENT_GRAM_T (default 1; 0 = A/B off): a Gram-form block's T = g^T h2 (bn3's sum(g xhat3) and conv3's weight
+# gradient both come from it) is accumulated by the kernel that writes g -- the NEXT block's conv1 dgrad with the
+# fused BN-backward epilogue (conv_stream.hip modes 6 / 7, BNBwdFuse(gramt=)) -- instead of a pass of its own that
+# reads all of g back (ops/bn_gram.py gram_T). Bottleneck width p = 64 (ResNet-50's layer 1); the producer marks the
+# block `_T_done`, the block's backward then takes the workspace T and clears the mark; without the mark (fp8
+# dgrad, IMAGENT_CONV_STREAM=0, a successor that did not run the fused form) gram_T runs as before
+_GRAM_T = os.environ.get("IMAGENT_GRAM_T", "1") != "0"
+
+
+def _gram_t_target(prev, conv, nox, fp8, x2):
+    """(h2, T) of the previous block when this block's conv1 dgrad (``conv``) can also form its T, else None: the
+    conditions of conv_plan.h gramt_plan, so the request never fails."""
+    gt = getattr(prev, "_gram_t", None)
+    if not (_GRAM_T and nox and gt is not None and fp8 is None) or _conv._NOSTREAM or _conv.deterministic():
+        return None
+    h2, T = gt
+    p = h2.shape[-1]
+    if not (p == 64 and conv.in_channels == 4 * p and conv.kh == 1 and conv.kw == 1 and conv.stride == 1
+            and conv.padding == 0 and (conv.out_channels == 64 or (conv.out_channels == 128 and x2 is None))):
+        return None
+    return h2, T
+
+
+def _take_T(block, dout, h2):
+    """T = g^T h2 for a block whose successor's dgrad ran without x3: the workspace T that dgrad accumulated
+    (``_T_done``, cleared here: ``gram_T(formed=True)`` launches nothing), else formed now by its own pass over g;
+    None when the slab holds sum(g xhat3)."""
+    if not getattr(block, "_bnb_nox", False):
+        return None
+    done = getattr(block, "_T_done", False)
+    block._T_done = False
+    return gram_T(dout, h2, out=_gws(block, 0), formed=done)
 
 
 def _next1_target(block, conv, q):
@@ -356,6 +388,9 @@ class BlockFn(torch.autograd.Function):
         block._bn_rows = rows
         # what the next block's backward needs to finish this block's last BN
         block._last_bn = (a, ad, ym) if fuse_next else None
+        # ... and to form this block's T = g^T h2 in that dgrad (IMAGENT_GRAM_T): conv3's input and the zeroed workspace
+        block._gram_t = (h, gws[0]) if (gram and fuse_next and gws is not None) else None
+        block._T_done = False
         block._bnb_done = False
         ctx.block = block
         ctx.xbn = xbn
@@ -396,7 +431,7 @@ class BlockFn(torch.autograd.Function):
             if premasked and ctx.gram and fuse:
                 # bn3 in the Gram form (as for identity blocks below); the downsample BN alone gets an apply pass:
                 # its reductions (sum g, sum g xhat_d) sit in bn3's slab rows 1, 2 (read there, sgx_row=2)
-                T = gram_T(dout, outs[-1], out=_gws(block, 0)) if getattr(block, "_bnb_nox", False) else None
+                T = _take_T(block, dout, outs[-1])
                 dA = gram_coef(bn_l, dout, T=T, w3=conv_l.w_bf16 if T is not None else None, hs=ctx.h2sum)
                 dAd, _ = bn_apply_backward(dout, ad, None, ds[1], None, 1, slab_of=bn_l, sgx_row=2)
                 dAd8 = None
@@ -421,7 +456,7 @@ class BlockFn(torch.autograd.Function):
         elif premasked and ctx.gram and fuse:
             # dx3 kept as (g, A, B, c): no apply pass (ops/bn_gram.py); when the next block's dgrad ran without x3,
             # sum(g xhat3) comes from T = g^T h2 (formed here, reused by the weight gradient)
-            T = gram_T(dout, outs[-1], out=_gws(block, 0)) if getattr(block, "_bnb_nox", False) else None
+            T = _take_T(block, dout, outs[-1])
             dA = gram_coef(bn_l, dout, T=T, w3=conv_l.w_bf16 if T is not None else None, hs=ctx.h2sum)
             dX = dout
         elif premasked:
@@ -433,8 +468,10 @@ class BlockFn(torch.autograd.Function):
             dA, dX = bn_act_backward(dout, a_last, x, out, bn_l, None, 1, True)  # dX = masked dout
         streams.flush_deferred()  # the next block's conv1 wgrad, after this memory-bound BN pass
         block._last_bn = None
+        block._gram_t = None
         block._bnb_done = False
         block._bnb_nox = False
+        block._T_done = False
         xbn = ctx.xbn  # xbn[i]: conv i's input is BN(acts[i - 1]) + ReLU applied on its operand path
         g_read = None  # side-stream event after the Gram wgrad's last read of dout (= dX)
         for i in range(n - 1, -1, -1):
@@ -474,8 +511,9 @@ class BlockFn(torch.autograd.Function):
                     pds = prev.downsample
                     # the previous block's bn3 backward takes the Gram form: sum(g xhat3) from g^T h2, x3 not read
                     nox = _GRAM_NOX and getattr(prev, "_gram", False) and pym is not None
+                    gt = _gram_t_target(prev, conv, nox, _dg8(dA8, conv), pad_)
                     fz = BNBwdFuse(None if nox else pa, pbn, y=pym, x2=pad_,
-                                   bn2=pds[1] if pds is not None else None)
+                                   bn2=pds[1] if pds is not None else None, gramt=gt)
                 if g_read is not None:
                     torch.cuda.current_stream().wait_event(g_read)
                 igemm_dgrad(dA, conv.wt_bf16, (H, W), conv.stride, conv.padding, conv.kh, conv.kw, out=dX,
@@ -489,4 +527,5 @@ class BlockFn(torch.autograd.Function):
                 if fz is not None:
                     prev._bnb_done = True
                     prev._bnb_nox = nox
+                    prev._T_done = fz.gramt is not None  # T sits in prev's workspace: its backward skips gram_T
         return dX, None

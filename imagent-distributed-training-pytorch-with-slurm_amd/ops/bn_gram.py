@@ -63,9 +63,14 @@ class GramBN:
         self.g, self.coef, self.T = g, coef, T
 
 
-def gram_T(g: torch.Tensor, h2: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-    """T = g^T h2 [4p][p] fp32 (conv3's weight-gradient GEMM), on the current stream (``out``: zeroed)."""
+def gram_T(g: torch.Tensor, h2: torch.Tensor, out: torch.Tensor = None, formed: bool = False) -> torch.Tensor:
+    """T = g^T h2 [4p][p] fp32 (conv3's weight-gradient GEMM), on the current stream (``out``: zeroed).
+    ``formed``: the kernel that wrote g has already accumulated T into ``out`` (``BNBwdFuse(gramt=)``, ops/block.py
+    IMAGENT_GRAM_T): nothing is launched and g is not read."""
     C4, p = g.shape[-1], h2.shape[-1]
+    if formed:
+        assert out is not None and tuple(out.shape) == (C4, p), "gram_T(formed=True) needs the accumulated T"
+        return out
     T = out if out is not None else torch.zeros((C4, p), device=g.device, dtype=torch.float32)
     igemm_wgrad(g, h2, T, 1, 0, 1, 1, splits=_splits(g.shape[-1], h2.shape[-1]))
     return T

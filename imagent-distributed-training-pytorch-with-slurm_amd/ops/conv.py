@@ -329,12 +329,15 @@ class BNBwdFuse:
 
     x: BN input; y: the ReLU mask of the BN(+add)+ReLU output as bits (uint8, numel / 8, written by the
     forward's ``bn_act_forward(ym=)``; ``ops.bn.relu_mask_bits``), None: mask recomputed from x with
-    gamma/beta (plain BN+ReLU); x2/bn2: the downsample BN branch of a fused residual (mode 2)."""
+    gamma/beta (plain BN+ReLU); x2/bn2: the downsample BN branch of a fused residual (mode 2).
+    gramt = (h2 [.., p] bf16, T [C, p] fp32, zeroed): the same launch also accumulates T += g^T h2 over the gradient
+    g it stores (:func:`ops.bn_gram.gram_T` without its pass over g); only the accumulating dgrad without ``x`` on
+    the streaming 1x1 kernel has it (conv_plan.h gramt_plan), any other call with it raises (code -125)."""
 
-    __slots__ = ("x", "y", "bn", "x2", "bn2")
+    __slots__ = ("x", "y", "bn", "x2", "bn2", "gramt")
 
-    def __init__(self, x, bn, y=None, x2=None, bn2=None):
-        self.x, self.bn, self.y, self.x2, self.bn2 = x, bn, y, x2, bn2
+    def __init__(self, x, bn, y=None, x2=None, bn2=None, gramt=None):
+        self.x, self.bn, self.y, self.x2, self.bn2, self.gramt = x, bn, y, x2, bn2, gramt
 
     def fill(self, a) -> None:
         w = self.bn.work
@@ -351,6 +354,13 @@ class BNBwdFuse:
         a.bnbeta = self.bn.bias.data_ptr()
         a.bnx2 = _lib.ptr(self.x2)
         a.bnsave2 = self.bn2.work.save.data_ptr() if self.x2 is not None else None
+        if self.gramt is not None:
+            h2, T = self.gramt
+            p = h2.shape[-1]
+            assert h2.dtype == torch.bfloat16 and h2.is_contiguous() and h2.numel() == a.M * p, (h2.shape, a.M)
+            assert T.dtype == torch.float32 and T.is_contiguous() and T.numel() == a.Nout * p, (T.shape, a.Nout, p)
+            assert not _DET, "gramt: T accumulates through float atomics"
+            a.gt_h2, a.gt_T, a.gt_p = h2.data_ptr(), T.data_ptr(), p
 
 
 def igemm_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, stride: int, pad: int, KH: int,
