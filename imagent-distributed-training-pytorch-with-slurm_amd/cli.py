@@ -61,6 +61,23 @@ def build_parser() -> argparse.ArgumentParser:
                    help="records stored at another size than --image-size are bilinearly resampled on the GPU "
                         "(fused into the normalise kernel) instead of cropped: e.g. 320^2 records for 448^2 "
                         "training halve the host gather bytes (profiles/loader_throughput.md)")
+    p.add_argument("--random-resized-crop", action="store_true",
+                   help="RandomResizedCrop train augmentation: a random box per sample (area fraction --rrc-scale, "
+                        "aspect --rrc-ratio), resampled to --image-size with an antialiased filter, fused with the "
+                        "normalise and --flip in one HIP kernel; validation takes the --val-center-crop box through "
+                        "the same antialiased filter. Takes precedence over --record-resize and the same-scale crop. "
+                        "Cost at 4096 img, 448^2 -> 224^2: profiles/rrc_normalize.md")
+    p.add_argument("--rrc-scale", type=float, nargs=2, default=[0.08, 1.0], metavar=("LO", "HI"),
+                   help="RandomResizedCrop: box area as a fraction of the source image")
+    p.add_argument("--rrc-ratio", type=float, nargs=2, default=[0.75, 1.3333], metavar=("LO", "HI"),
+                   help="RandomResizedCrop: box aspect ratio w / h, log-uniform (relative to the stored image: "
+                        "records are aspect-squashed squares)")
+    p.add_argument("--val-center-crop", type=float, default=1.0, metavar="FRAC",
+                   help="validation: the centred box of this fraction of each side, antialiased to --image-size "
+                        "(0.875 = the usual 224 of 256); 1.0 with --random-resized-crop off: the existing path")
+    p.add_argument("--source-size", type=int, default=None, metavar="N",
+                   help="--data imagenet: the size the JPEG folder loader decodes to (default --image-size), so that "
+                        "--random-resized-crop has pixels to crop from; records and synthetic data hold their own")
     # --- optimisation ---
     p.add_argument("--optimizer", default="sgd",
                    choices=["sgd", "lars", "adam", "adamw", "adagrad", "rmsprop", "adadelta", "asgd", "nadam"])

@@ -753,6 +753,258 @@ __global__ __launch_bounds__(256) void resize_normalize_kernel(const uint8_t* __
     }
 }
 
+// --------------------------------------------- random-resized-crop + normalize (uint8)
+// RandomResizedCrop fused into the normalize (--random-resized-crop, data/augment.py draws the boxes): in uint8
+// [B][Hs][Ws][3], boxes int32 [B][4] = (top, left, h, w) -> out [B][H][W][Cp] (bf16 or fp32), every sample's box
+// resampled to H x W with the antialiased triangle filter ("crop, then resize": torch's interpolate(bilinear,
+// antialias=True, align_corners=False) of the crop), then (v/255 - mean) * istd, optional horizontal flip. Per
+// axis, a box of n source pixels onto m outputs: s = n / m, sup = max(s, 1), c = (i + 0.5) s, taps j in
+// [max(0, int(c - sup + 0.5)), min(n, int(c + sup + 0.5))) relative to the box, weight max(0, 1 - |j - c + 0.5| / sup)
+// normalised to sum 1 -- taps are clamped to the BOX, so with the box clamped into the image no value of `boxes`
+// reads outside `in`. For s <= 1 this is resize_normalize_kernel's bilinear filter, for n == m the weights are
+// exactly 1 and 0 (a plain crop, bit for bit normalize_kernel's result).
+// c is formed as an integer part and a fraction, (2i + 1) n = q (2m) + rem, so that the tap distances keep ~1e-7
+// absolute at any coordinate (c itself in fp32 is good to 1e-5 at 448 px: 3e-3 grey levels on a hard edge).
+struct RrcTaps {
+    int lo, n;  // taps [lo, lo + n) relative to the box
+    float d0;   // tap lo's distance j - c + 0.5; tap lo + k's is d0 + k
+};
+
+__device__ __forceinline__ RrcTaps rrc_taps(int i, int n, int m, float sup) {
+    const uint32_t num = (2u * (uint32_t)i + 1u) * (uint32_t)n, den = 2u * (uint32_t)m;
+    const uint32_t q = num / den;
+    const float frac = (float)(num - q * den) / (float)den;
+    const float c = (float)q + frac;
+    RrcTaps t;
+    t.lo = max(0, (int)(c - sup + 0.5f));
+    t.n = min(n, (int)(c + sup + 0.5f)) - t.lo;
+    t.d0 = (float)(t.lo - (int)q) + (0.5f - frac);
+    return t;
+}
+
+__device__ __forceinline__ float rrc_w(float d, float isup) { return fmaxf(0.f, 1.f - fabsf(d * isup)); }
+
+template <typename T, int CP>  // CP 4 / 8: one vector store per pixel; 0: Cp channels, one by one
+__device__ __forceinline__ void rrc_store(T* __restrict__ o, float c0, float c1, float c2, int Cp) {
+    if constexpr (sizeof(T) == 2) {
+        if constexpr (CP == 8) {
+            *reinterpret_cast<u32x4*>(o) = u32x4{pack_bf2(c0, c1), pack_bf2(c2, 0.f), 0u, 0u};
+        } else if constexpr (CP == 4) {
+            *reinterpret_cast<u32x2*>(o) = u32x2{pack_bf2(c0, c1), pack_bf2(c2, 0.f)};
+        } else {
+            o[0] = f2bf(c0);
+            o[1] = f2bf(c1);
+            o[2] = f2bf(c2);
+            for (int c = 3; c < Cp; ++c) o[c] = 0;
+        }
+    } else {
+        if constexpr (CP == 4 || CP == 8) {
+            *reinterpret_cast<f32x4*>(o) = f32x4{c0, c1, c2, 0.f};
+            if constexpr (CP == 8) *reinterpret_cast<f32x4*>(o + 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            o[0] = c0;
+            o[1] = c1;
+            o[2] = c2;
+            for (int c = 3; c < Cp; ++c) o[c] = 0.f;
+        }
+    }
+}
+
+// Separable, staged in LDS: a block owns `band` output rows of one image. It filters the source rows of the box
+// that the band's vertical taps reach horizontally into LDS (fp32 [row][W][3]; one thread per output column, its
+// column's weights formed once and kept for every row), then filters vertically from LDS, normalises and stores
+// (G == 4: four pixels per thread and two 16-B stores, as normalize4_kernel; bf16, Cp 4, W % 4 == 0). A per-pixel
+// 2-D gather would read (taps_y x taps_x) x 3 bytes per output pixel. Boxes differ per sample, so the scales and
+// the weights are per block, formed on the fly. A band whose source rows do not fit `lds_floats` (vertical scales
+// past ~2 at 224 px) takes the generic per-pixel gather instead: any scale is correct, the production ones are fast.
+template <typename T, int CP, int G>
+__global__ __launch_bounds__(256) void rrc_normalize_kernel(const uint8_t* __restrict__ in, T* __restrict__ out,
+                                                            const int* __restrict__ boxes,
+                                                            const uint8_t* __restrict__ flip, int Hs, int Ws, int H,
+                                                            int W, int Cp, int band, int nbands, int lds_floats,
+                                                            float m0, float m1, float m2, float is0, float is1,
+                                                            float is2) {
+    extern __shared__ float rrc_rows[];
+    const int tid = threadIdx.x;
+    const uint32_t b = blockIdx.x / (uint32_t)nbands;
+    const int r0 = (int)(blockIdx.x - b * (uint32_t)nbands) * band, nb = min(band, H - r0);
+    // the box, clamped into the image: 1 <= h <= Hs, 0 <= top <= Hs - h (likewise w, left)
+    const int bh = min(max(boxes[4 * b + 2], 1), Hs), bw = min(max(boxes[4 * b + 3], 1), Ws);
+    const int top = min(max(boxes[4 * b], 0), Hs - bh), left = min(max(boxes[4 * b + 1], 0), Ws - bw);
+    const bool fl = flip && flip[b];
+    const float supy = fmaxf((float)bh / (float)H, 1.f), supx = fmaxf((float)bw / (float)W, 1.f);
+    const float isy = 1.f / supy, isx = 1.f / supx;
+    const uint8_t* img = in + ((size_t)b * Hs + top) * Ws * 3 + (size_t)left * 3;  // the box's corner
+    const uint8_t* in_end = in + (size_t)(gridDim.x / (uint32_t)nbands) * Hs * Ws * 3;
+    T* orow = out + (size_t)b * H * W * Cp;
+    // source rows of the box that the band reaches: [ylo, yhi)
+    const RrcTaps tf = rrc_taps(r0, bh, H, supy), tl = rrc_taps(r0 + nb - 1, bh, H, supy);
+    const int ylo = tf.lo, yhi = tl.lo + tl.n, nrows = yhi - ylo;
+
+    if ((long)nrows * W * 3 > (long)lds_floats) {  // generic: the 2-D gather, one output pixel per thread
+        for (int it = tid; it < nb * W; it += 256) {
+            const int rr = it / W, w = it - rr * W, sw = fl ? W - 1 - w : w;
+            const RrcTaps ty = rrc_taps(r0 + rr, bh, H, supy), tx = rrc_taps(sw, bw, W, supx);
+            float wsx = 0.f, wsy = 0.f;
+            for (int k = 0; k < tx.n; ++k) wsx += rrc_w(tx.d0 + (float)k, isx);
+            const float invx = 1.f / wsx;
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            for (int j = 0; j < ty.n; ++j) {
+                const float wj = rrc_w(ty.d0 + (float)j, isy);
+                wsy += wj;
+                const uint8_t* p = img + ((size_t)(ty.lo + j) * Ws + tx.lo) * 3;
+                float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+                for (int k = 0; k < tx.n; ++k) {
+                    const float wk = rrc_w(tx.d0 + (float)k, isx);
+                    h0 += wk * (float)p[3 * k];
+                    h1 += wk * (float)p[3 * k + 1];
+                    h2 += wk * (float)p[3 * k + 2];
+                }
+                a0 += wj * (h0 * invx);
+                a1 += wj * (h1 * invx);
+                a2 += wj * (h2 * invx);
+            }
+            const float invy = 1.f / wsy;
+            rrc_store<T, CP>(orow + ((size_t)(r0 + rr) * W + w) * Cp, (a0 * invy * (1.f / 255.f) - m0) * is0,
+                             (a1 * invy * (1.f / 255.f) - m1) * is1, (a2 * invy * (1.f / 255.f) - m2) * is2, Cp);
+        }
+        return;
+    }
+
+    // horizontal: thread -> (output column, row lane); 256 / W row lanes when W < 256
+    {
+        const int cpp = min(W, 256), nsub = 256 / cpp;
+        const int col = tid % cpp, rsub = tid / cpp;
+        const bool few = supx <= 2.f;  // at most 5 taps: every load of a trip issued before any is used
+        if (rsub < nsub)
+            for (int ox = col; ox < W; ox += cpp) {
+                const RrcTaps tx = rrc_taps(ox, bw, W, supx);
+                float ws = 0.f;
+                for (int k = 0; k < tx.n; ++k) ws += rrc_w(tx.d0 + (float)k, isx);
+                const float inv = 1.f / ws;
+                const uint8_t* p0 = img + ((size_t)ylo * Ws + tx.lo) * 3;
+                if (few) {
+                    // the taps' 3 x n <= 15 bytes are consecutive: ONE unaligned 16-byte load per (row, column)
+                    // instead of 15 byte loads (the pass is bound by load instructions, not by bytes: 2,230 us
+                    // with byte loads at 4096 img, profiles/rrc_normalize.md); tap k's channel c is byte 3 k + c.
+                    // Slots past the taps hold in-bounds bytes at weight 0. The last 16 bytes of the tensor are
+                    // the one place where the window would leave `in`: byte loads from clamped addresses there.
+                    float wk[5];
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) wk[k] = k < tx.n ? rrc_w(tx.d0 + (float)k, isx) : 0.f;
+                    // NR rows per trip, their loads issued before any is used: one window per thread in flight
+                    // left the pass waiting on L2 / HBM latency. Rows past the band load the last row again.
+                    constexpr int NR = 5;
+                    for (int row = rsub; row < nrows; row += NR * nsub) {
+                        uint32_t q[NR][4];
+#pragma unroll
+                        for (int r = 0; r < NR; ++r) {
+                            const uint8_t* p = p0 + (size_t)min(row + r * nsub, nrows - 1) * Ws * 3;
+                            if (p + 16 <= in_end) {
+                                __builtin_memcpy(q[r], p, 16);
+                            } else {
+                                q[r][0] = q[r][1] = q[r][2] = q[r][3] = 0u;
+#pragma unroll
+                                for (int e = 0; e < 15; ++e)
+                                    q[r][e >> 2] |= (uint32_t)p[min(e, 3 * tx.n - 1)] << (8 * (e & 3));
+                            }
+                        }
+#pragma unroll
+                        for (int r = 0; r < NR; ++r) {
+                            float a[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int k = 0; k < 5; ++k)
+#pragma unroll
+                                for (int c = 0; c < 3; ++c)
+                                    a[c] += wk[k] * (float)((q[r][(3 * k + c) >> 2] >> (8 * ((3 * k + c) & 3))) & 0xffu);
+                            if (row + r * nsub < nrows) {
+                                float* d = rrc_rows + ((row + r * nsub) * W + ox) * 3;
+                                d[0] = a[0] * inv;
+                                d[1] = a[1] * inv;
+                                d[2] = a[2] * inv;
+                            }
+                        }
+                    }
+                } else {
+                    for (int row = rsub; row < nrows; row += nsub) {
+                        const uint8_t* p = p0 + (size_t)row * Ws * 3;
+                        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+                        for (int k = 0; k < tx.n; ++k) {
+                            const float w = rrc_w(tx.d0 + (float)k, isx);
+                            a0 += w * (float)p[3 * k];
+                            a1 += w * (float)p[3 * k + 1];
+                            a2 += w * (float)p[3 * k + 2];
+                        }
+                        float* d = rrc_rows + (row * W + ox) * 3;
+                        d[0] = a0 * inv;
+                        d[1] = a1 * inv;
+                        d[2] = a2 * inv;
+                    }
+                }
+            }
+    }
+    __syncthreads();
+
+    // vertical from LDS, normalise, store: G consecutive pixels of an output row per thread
+    const int gpr = W / G;
+    for (int it = tid; it < nb * gpr; it += 256) {
+        const int rr = it / gpr, g = it - rr * gpr;
+        const RrcTaps ty = rrc_taps(r0 + rr, bh, H, supy);
+        const int lo = max(ty.lo, ylo), hi = min(ty.lo + ty.n, yhi);  // inside the staged rows by construction
+        const int sw0 = fl ? W - G - G * g : G * g;                    // first filtered column of the group
+        float acc[3 * G], ws = 0.f;
+#pragma unroll
+        for (int e = 0; e < 3 * G; ++e) acc[e] = 0.f;
+        for (int j = lo; j < hi; ++j) {
+            const float wj = rrc_w(ty.d0 + (float)(j - ty.lo), isy);
+            ws += wj;
+            const float* s = rrc_rows + ((j - ylo) * W + sw0) * 3;
+#pragma unroll
+            for (int e = 0; e < 3 * G; ++e) acc[e] += wj * s[e];
+        }
+        const float inv = 1.f / ws;
+        T* o = orow + ((size_t)(r0 + rr) * W + G * g) * Cp;
+        if constexpr (G == 4) {  // bf16, Cp 4: pixel k of the group is filtered column sw0 + (fl ? 3 - k : k)
+            u32x2 px[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float c0 = (acc[3 * k] * inv * (1.f / 255.f) - m0) * is0;
+                const float c1 = (acc[3 * k + 1] * inv * (1.f / 255.f) - m1) * is1;
+                const float c2 = (acc[3 * k + 2] * inv * (1.f / 255.f) - m2) * is2;
+                px[k] = u32x2{pack_bf2(c0, c1), pack_bf2(c2, 0.f)};
+            }
+            u32x4* dst = reinterpret_cast<u32x4*>(o);
+            if (fl) {
+                dst[0] = u32x4{px[3][0], px[3][1], px[2][0], px[2][1]};
+                dst[1] = u32x4{px[1][0], px[1][1], px[0][0], px[0][1]};
+            } else {
+                dst[0] = u32x4{px[0][0], px[0][1], px[1][0], px[1][1]};
+                dst[1] = u32x4{px[2][0], px[2][1], px[3][0], px[3][1]};
+            }
+        } else {
+            rrc_store<T, CP>(o, (acc[0] * inv * (1.f / 255.f) - m0) * is0, (acc[1] * inv * (1.f / 255.f) - m1) * is1,
+                             (acc[2] * inv * (1.f / 255.f) - m2) * is2, Cp);
+        }
+    }
+}
+
+// the band height and the LDS bytes of rrc_normalize_kernel. A band of R rows at vertical scale s reaches at most
+// (R - 1) s + 2 max(s, 1) + 1 source rows; no box is larger than the image, so s <= Hs / H and the launch asks for
+// just those rows (448 -> 224 px, R = 8: 19 rows x 224 x 12 B = 50 KB, three blocks per CU), at most `cap` bytes --
+// bands past it take the generic path. R = 8 / 4 / 2 at 4096 img, default boxes: 1,516 / 1,679 / 2,315 us
+// (profiles/rrc_normalize.md). IMAGENT_RRC_BAND / IMAGENT_RRC_LDS_KB (the cap, <= 64): A/B in one process, read on
+// every call.
+static void rrc_config(int Hs, int H, int W, int* band, int* lds_bytes) {
+    const char* e = getenv("IMAGENT_RRC_BAND");
+    const char* l = getenv("IMAGENT_RRC_LDS_KB");
+    *band = min(e && *e ? min(max(atoi(e), 1), 64) : 8, H);
+    const long cap = (l && *l ? min(max(atoi(l), 1), 64) : 64) * 1024L;
+    const double s = (double)Hs / (double)H;
+    const long rows = (long)((*band - 1) * s + 2.0 * (s > 1.0 ? s : 1.0) + 1.0);
+    const long need = rows * W * 12L;
+    *lds_bytes = (int)(need < cap ? (need < 1024 ? 1024 : need) : cap);
+}
+
 // ------------------------------------------------- batched weight transposes
 // dst[ci][t][co] = src[co][t][ci]  for every conv in the descriptor table.
 struct TDesc {
@@ -1029,6 +1281,40 @@ IMK_EXPORT int imk_normalize_u8(const void* in, void* out, const int* crop, cons
                        (hipStream_t)stream, (const uint8_t*)in, (bf16_t*)out, crop,
                        (const uint8_t*)flip, B, Hs, Ws, H, W, Cp, mean[0], mean[1], mean[2],
                        1.f / std[0], 1.f / std[1], 1.f / std[2]);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
+// RandomResizedCrop + normalize: boxes int32 [B][4] = (top, left, h, w) on the device (clamped into the image by
+// the kernel), out bf16 (out_f32 0) or fp32 (1) [B][H][W][Cp]
+IMK_EXPORT int imk_rrc_normalize_u8(const void* in, void* out, const int* boxes, const void* flip, int B, int Hs,
+                                    int Ws, int H, int W, int Cp, const float* mean, const float* std, int out_f32,
+                                    void* stream) {
+    if (B < 0 || Hs < 1 || Ws < 1 || H < 1 || W < 1 || Cp < 3 || !boxes) return -1;
+    // rrc_taps forms (2 i + 1) n in 32 bits
+    if (2L * H * Hs >= (1L << 31) || 2L * W * Ws >= (1L << 31)) return -101;
+    if (B == 0) return 0;
+    int band, lds;
+    rrc_config(Hs, H, W, &band, &lds);
+    const int nbands = (H + band - 1) / band;
+    if ((long)B * nbands >= (1L << 31)) return -101;
+    const dim3 g((uint32_t)B * nbands), bl(256);
+    const float m0 = mean[0], m1 = mean[1], m2 = mean[2], i0 = 1.f / std[0], i1 = 1.f / std[1], i2 = 1.f / std[2];
+#define IMK_RRC(T, CP, G)                                                                                          \
+    hipLaunchKernelGGL((rrc_normalize_kernel<T, CP, G>), g, bl, lds, (hipStream_t)stream, (const uint8_t*)in,      \
+                       (T*)out, boxes, (const uint8_t*)flip, Hs, Ws, H, W, Cp, band, nbands, lds / 4, m0, m1, m2,  \
+                       i0, i1, i2)
+    if (out_f32) {
+        if (Cp == 4) IMK_RRC(float, 4, 1);
+        else if (Cp == 8) IMK_RRC(float, 8, 1);
+        else IMK_RRC(float, 0, 1);
+    } else {
+        if (Cp == 4 && W % 4 == 0) IMK_RRC(bf16_t, 4, 4);
+        else if (Cp == 4) IMK_RRC(bf16_t, 4, 1);
+        else if (Cp == 8) IMK_RRC(bf16_t, 8, 1);
+        else IMK_RRC(bf16_t, 0, 1);
+    }
+#undef IMK_RRC
     IMK_CHECK_LAUNCH();
     return 0;
 }

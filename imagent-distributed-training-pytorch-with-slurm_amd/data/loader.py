@@ -12,7 +12,9 @@ CPU ``ToTensor/Normalize`` (``imagenet.py:119-120, 280-283, 346-359``):
   current step computes; the compute stream waits on an event, never on the
   host;
 * normalisation (``(x/255 - mean)/std``), the NHWC channel padding for the
-  stem and optional random crop / horizontal flip are one HIP kernel;
+  stem and optional random crop / horizontal flip are one HIP kernel; so is
+  RandomResizedCrop (``rrc=``: boxes drawn on the device by ``data/augment.py``,
+  crop + antialiased resize + normalise + flip fused, ``ops.misc.rrc_normalize_u8``);
 * workers are persistent (the reference re-forks 10 workers every epoch).
 """
 
@@ -33,7 +35,8 @@ class InputTransform:
     """uint8 [B,H,W,3] (on the compute device) -> model input."""
 
     def __init__(self, backend: str, size: Tuple[int, int], mean=MEAN, std=STD, cpad: int = 8,
-                 flip: bool = False, dtype=torch.float32, resize: bool = False):
+                 flip: bool = False, dtype=torch.float32, resize: bool = False, rrc=None,
+                 center_frac: Optional[float] = None, seed: int = 0, rank: int = 0):
         self.backend, self.size = backend, tuple(size)
         self.mean, self.std, self.cpad = tuple(mean), tuple(std), cpad
         self.flip = flip
@@ -41,8 +44,84 @@ class InputTransform:
         # resize: an image of another size is bilinearly resampled to `size` (records stored smaller than the
         # model input, --record-resize) instead of randomly cropped
         self.resize = resize
+        # rrc = (scale, ratio): RandomResizedCrop (data/augment.py) -- a random box per sample, resampled to
+        # `size` with the antialiased filter; it takes precedence over `resize` and the same-scale crop.
+        # center_frac: the centred box of that fraction of each side instead, through the same antialiased path
+        # (validation: no randomness, no flip).
+        if rrc is not None:
+            from .augment import check_ranges
+            rrc = (tuple(float(v) for v in rrc[0]), tuple(float(v) for v in rrc[1]))
+            check_ranges(*rrc)
+        if center_frac is not None and not (0.0 < center_frac <= 1.0):
+            raise ValueError(f"centre crop fraction {center_frac}: need 0 < frac <= 1")
+        self.rrc, self.center_frac = rrc, center_frac
+        # the random boxes and their flip mask come from a generator of the transform's own, on the compute
+        # device, reseeded from (seed, rank, epoch): a resumed run repeats the epoch's boxes
+        self.seed, self.rank, self.epoch = int(seed), int(rank), 0
+        self._gen = None
+        self._center = {}
 
-    def __call__(self, u8: torch.Tensor) -> torch.Tensor:
+    def _epoch_seed(self) -> int:
+        return (self.seed * 0x9E3779B1 + self.rank * 0x85EBCA6B + self.epoch * 0xC2B2AE35 + 1) % (2 ** 63 - 1)
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+        if self._gen is not None:
+            self._gen.manual_seed(self._epoch_seed())
+
+    def _generator(self, device) -> torch.Generator:
+        if self._gen is None or self._gen.device != torch.device(device):
+            self._gen = torch.Generator(device=device)
+            self._gen.manual_seed(self._epoch_seed())
+        return self._gen
+
+    def _boxed(self, u8: torch.Tensor, boxes, flip) -> torch.Tensor:
+        """The box path: RandomResizedCrop (rrc) or the centre box (center_frac), antialiased resample to `size`."""
+        from .augment import center_box, sample_boxes
+        B, H, W, _ = u8.shape
+        oh, ow = self.size
+        dev = u8.device
+        if boxes is None:
+            if self.rrc is not None:
+                boxes = sample_boxes(B, H, W, self.rrc[0], self.rrc[1], self._generator(dev), dev)
+            else:
+                key = (dev, B, H, W)
+                if key not in self._center:
+                    self._center = {key: torch.tensor([center_box(H, W, self.center_frac)] * B,
+                                                      dtype=torch.int32).to(dev)}
+                boxes = self._center[key]
+        if flip is None and self.flip and self.rrc is not None:
+            flip = (torch.rand(B, generator=self._generator(dev), device=dev) < 0.5).to(torch.uint8)
+        if self.backend in ("hip", "hip_f32"):
+            from ..ops.misc import rrc_normalize_u8
+            return rrc_normalize_u8(u8, (oh, ow), self.cpad, self.mean, self.std, boxes, flip,
+                                    dtype=torch.float32 if self.backend == "hip_f32" else torch.bfloat16)
+        # torch: crop each sample, interpolate(antialias=True), batched over samples with equal box shapes
+        x = u8.permute(0, 3, 1, 2)
+        out = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=dev)
+        bl = boxes.tolist()
+        groups = {}
+        for i, (t, l, h, w) in enumerate(bl):
+            groups.setdefault((h, w), []).append(i)
+        for (h, w), idx in groups.items():
+            crops = torch.stack([x[i, :, bl[i][0]:bl[i][0] + h, bl[i][1]:bl[i][1] + w] for i in idx]).float()
+            out[idx] = torch.nn.functional.interpolate(crops, size=(oh, ow), mode="bilinear", antialias=True,
+                                                       align_corners=False)
+        m = torch.tensor(self.mean, dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+        s = torch.tensor(self.std, dtype=torch.float32, device=dev).view(1, 3, 1, 1)
+        out = (out / 255.0 - m) / s
+        if flip is not None:
+            out = torch.where(flip.view(-1, 1, 1, 1).bool(), out.flip(3), out)
+        return out.to(self.dtype).contiguous()
+
+    def __call__(self, u8: torch.Tensor, boxes: Optional[torch.Tensor] = None,
+                 flip: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``boxes`` (int32 [B, 4] = top, left, h, w) / ``flip`` (uint8 [B]): explicit draws for the box path
+        instead of the transform's own (comparing backends on identical draws)."""
+        if self.rrc is not None or self.center_frac is not None:
+            return self._boxed(u8, boxes, flip)
+        if boxes is not None or flip is not None:
+            raise ValueError("explicit boxes / flip need rrc= or center_frac=")
         B, H, W, _ = u8.shape
         oh, ow = self.size
         if self.backend in ("hip", "hip_f32"):

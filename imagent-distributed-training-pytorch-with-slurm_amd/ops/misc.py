@@ -295,6 +295,41 @@ def resize_normalize_u8(images: torch.Tensor, out_hw, cpad: int, mean: Sequence[
     return out
 
 
+def rrc_normalize_u8(images: torch.Tensor, out_hw, cpad: int, mean: Sequence[float], std: Sequence[float],
+                     boxes: torch.Tensor, flip: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     dtype=torch.bfloat16) -> torch.Tensor:
+    """uint8 [B, Hs, Ws, 3] -> NHWC [B, H, W, cpad] (bf16 or fp32): every sample's box ``boxes[b] = (top, left, h,
+    w)`` resampled to (H, W) with the antialiased triangle filter -- ``F.interpolate(crop, (H, W), mode='bilinear',
+    antialias=True, align_corners=False)``, "crop, then resize" -- fused with (x/255 - mean)/std and an optional
+    horizontal flip (RandomResizedCrop, ``data/augment.py``; csrc/kernels/misc.hip rrc_normalize_kernel).
+    ``boxes`` on the host are checked here (ValueError for a box outside the image) and copied; boxes on the device
+    are not synchronised on -- the kernel clamps them into the image, so no value reads out of bounds."""
+    B, Hs, Ws, _ = images.shape
+    H, W = out_hw
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"rrc_normalize_u8: dtype {dtype} (bf16 or fp32)")
+    if boxes.dim() != 2 or tuple(boxes.shape) != (B, 4):
+        raise ValueError(f"rrc_normalize_u8: boxes {tuple(boxes.shape)}, expected ({B}, 4)")
+    if not boxes.is_cuda:
+        bx = boxes.to(torch.int64)
+        t, l, h, w = bx.unbind(1)
+        bad = (t < 0) | (l < 0) | (h < 1) | (w < 1) | (t + h > Hs) | (l + w > Ws)
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0])
+            raise ValueError(f"rrc_normalize_u8: box {i} = {bx[i].tolist()} (top, left, h, w) lies outside the "
+                             f"{Hs}x{Ws} image")
+    boxes = boxes.to(device=images.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((B, H, W, cpad), device=images.device, dtype=dtype)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    _lib.check(_lib.kernels().imk_rrc_normalize_u8(images.data_ptr(), out.data_ptr(), boxes.data_ptr(), _lib.ptr(flip),
+                                                   B, Hs, Ws, H, W, cpad, C.cast(m, C.c_void_p),
+                                                   C.cast(s, C.c_void_p), 1 if out.dtype == torch.float32 else 0,
+                                                   _lib.stream_ptr()), "random-resized-crop + normalize")
+    return out
+
+
 def normalize_u8(images: torch.Tensor, out_hw, cpad: int, mean: Sequence[float], std: Sequence[float],
                  crop: Optional[torch.Tensor] = None, flip: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -217,6 +217,7 @@ class Trainer:
         if getattr(a, "fp8_wgrad", False) and (a.dtype != "fp8" or a.kernels == "torch"):
             raise SystemExit("--fp8-wgrad needs --dtype fp8 --kernels hip (the fp8 weight gradient reads the 1-byte "
                              f"copies of the fp8 forward and dgrad): got --dtype {a.dtype} --kernels {a.kernels}")
+        self._check_augmentation(a)
         torch.manual_seed(a.seed)  # imagenet.py:215
         self.topo = launcher.discover(a.launcher)
         if not a.quiet_banner:
@@ -237,6 +238,26 @@ class Trainer:
             if (self.is_master and a.tb_dir) else None
 
     # ------------------------------------------------------------- data
+    @staticmethod
+    def _check_augmentation(a):
+        """--random-resized-crop / --val-center-crop / --source-size: nonsensical values end the run here, not on
+        the first batch."""
+        from ..data.augment import check_ranges
+        try:
+            check_ranges(getattr(a, "rrc_scale", (0.08, 1.0)), getattr(a, "rrc_ratio", (0.75, 1.3333)))
+        except ValueError as e:
+            raise SystemExit(f"--rrc-scale / --rrc-ratio: {e}")
+        vc = getattr(a, "val_center_crop", 1.0)
+        if not (0.0 < vc <= 1.0):
+            raise SystemExit(f"--val-center-crop {vc}: need 0 < FRAC <= 1")
+        ss = getattr(a, "source_size", None)
+        if ss is not None and ss < 1:
+            raise SystemExit(f"--source-size {ss}: need a positive size")
+        if ss is not None and ss < a.image_size and not getattr(a, "random_resized_crop", False) \
+                and not getattr(a, "record_resize", False):
+            raise SystemExit(f"--source-size {ss} is smaller than --image-size {a.image_size}: only "
+                             "--random-resized-crop resamples the decoded images")
+
     def _build_data(self):
         a = self.args
         _master_print(self.is_master, "Initialize Dataloaders...")
@@ -269,9 +290,11 @@ class Trainer:
             self.train_set = RecordFile(os.path.join(root, "train.imrec"), threads=a.workers)
             self.val_set = RecordFile(os.path.join(root, "val.imrec"), threads=a.workers)
             H, W, _ = self.train_set.shape
-            if (H < size[0] or W < size[1]) and not getattr(a, "record_resize", False):
+            if (H < size[0] or W < size[1]) and not getattr(a, "record_resize", False) \
+                    and not getattr(a, "random_resized_crop", False):
                 raise SystemExit(f"records hold {H}x{W} images, smaller than --image-size {a.image_size} "
-                                 "(--record-resize: resample them on the GPU)")
+                                 "(--record-resize: resample them on the GPU; --random-resized-crop resamples "
+                                 "its boxes)")
             self.num_classes = self.train_set.num_classes
             self.n_train, self.n_val = len(self.train_set), len(self.val_set)
             self.train_sampler = ShardSampler(self.n_train, ws, rk, shuffle=True, seed=0)
@@ -279,8 +302,9 @@ class Trainer:
         else:
             from ..data.imagenet import ImageNetU8
             root = a.data_root or os.path.join(os.path.abspath(os.path.join(".", os.pardir)), "data/imagenet")
-            self.train_set = ImageNetU8(root, "train", size)
-            self.val_set = ImageNetU8(root, "val", size)
+            ss = getattr(a, "source_size", None) or a.image_size  # the decoded size (--source-size)
+            self.train_set = ImageNetU8(root, "train", (ss, ss))
+            self.val_set = ImageNetU8(root, "val", (ss, ss))
             self.num_classes = len(self.train_set.classes)
             self.n_train, self.n_val = len(self.train_set), len(self.val_set)
             # imagenet.py:346-347: shuffle=True for BOTH samplers (quirk Q2 kept)
@@ -295,14 +319,29 @@ class Trainer:
         if getattr(a, "fp8_wgrad", False) and self.kernels != "hip":
             raise SystemExit("--fp8-wgrad needs the HIP kernels (--kernels hip on a MI355X)")
         rs = getattr(a, "record_resize", False)
+        rrc = None
+        vc = getattr(a, "val_center_crop", 1.0)
+        if getattr(a, "random_resized_crop", False):
+            rrc = (tuple(a.rrc_scale), tuple(a.rrc_ratio))
+        # the validation centre box goes through the antialiased path whenever the train boxes do (or a fraction is
+        # asked for); with neither flag the transforms are the existing ones, byte for byte
+        center = vc if (rrc is not None or vc != 1.0) else None
         self.transform_train = InputTransform(self.kernels, size, cpad=resnet.ResNet.STEM_CPAD,
-                                              flip=a.flip, dtype=torch.float32, resize=rs)
+                                              flip=a.flip, dtype=torch.float32, resize=rs, rrc=rrc, seed=a.seed,
+                                              rank=rk)
         self.transform_val = InputTransform(self.kernels, size, cpad=resnet.ResNet.STEM_CPAD,
-                                            dtype=torch.float32, resize=rs)
+                                            dtype=torch.float32, resize=rs, center_frac=center)
+        if rrc is not None:
+            _master_print(self.is_master, "Augmentation: RandomResizedCrop scale ({:g}, {:g}) ratio ({:g}, {:g}){} "
+                          "-> {}x{}, antialiased".format(*rrc[0], *rrc[1], " + flip" if a.flip else "", *size))
+        if center is not None:
+            _master_print(self.is_master, "Validation: centre crop {:g} of each side -> {}x{}, antialiased"
+                          .format(center, *size))
 
     def _loaders(self, epoch: int):
         a = self.args
         self.train_sampler.set_epoch(epoch)   # imagenet.py:375 (val sampler stays at epoch 0)
+        self.transform_train.set_epoch(epoch)  # the epoch's RandomResizedCrop boxes and flips (a resume repeats them)
         if a.data == "synthetic":
             nt = self.train_sampler.num_batches(a.batch_size)
             nv = self.val_sampler.num_batches(a.batch_size)
