@@ -32,6 +32,7 @@
 // per channel per block at the end (the direct register epilogue measured
 // 285 of 544 us at R50 64@56, batch 1024).
 
+#include "conv_epilogue.h"
 #include "conv_igemm_impl.h"
 
 namespace {
@@ -45,14 +46,6 @@ constexpr int halo_pw(int W) { return (W % 16 == 0) ? W + 2 : ((W + 2 + 7) / 8) 
 constexpr int HALO_SP = 136;  // staged-epilogue row pitch, bytes (34 dwords: conflict-free 8-B writes)
 constexpr size_t halo_lds(int W, int R) {
     return (size_t)HALO_WB + (size_t)(R + 2) * halo_pw(W) * 128 + (size_t)R * W * HALO_SP;
-}
-
-__device__ __forceinline__ void unpack8(const u32x4 w, float (&v)[8]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[2 * k] = lo_bf(w[k]);
-        v[2 * k + 1] = hi_bf(w[k]);
-    }
 }
 
 template <int W, int R, int EPI>  // EPI 0: forward (+ shifted BN statistics), 1: fused BN backward, 2: + second BN branch
@@ -121,12 +114,7 @@ __global__ __launch_bounds__(512, 1) void halo3x3_kernel(const IGemmArgs a, int 
                 const int prow = pix / PCOLS, pcol = pix - prow * PCOLS;
                 const int q = prow * PW + pcol;
                 u32x4 v = pr[i];
-                if (xbn && pv[i]) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        v[k] = pack_bf2(fmaxf(fmaf(lo_bf(v[k]), xsc[2 * k], xsh[2 * k]), 0.f),
-                                        fmaxf(fmaf(hi_bf(v[k]), xsc[2 * k + 1], xsh[2 * k + 1]), 0.f));
-                }
+                if (xbn && pv[i]) v = xbn_apply(v, xsc, xsh);
                 *reinterpret_cast<u32x4*>(sP + q * 128 + ((c ^ (q & 7)) << 4)) = v;
             }
         }
@@ -344,8 +332,7 @@ __global__ __launch_bounds__(512, 1) void halo3x3_kernel(const IGemmArgs a, int 
         const int qq = tid >> 6, n = tid & 63, c = n >> 3, k = n & 7;
         float sum = 0.f;
         for (int u = c; u < 512; u += 8) sum += red[(qq * 512 + u) * 8 + k];
-        float* st = a.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * (EPI >= 1 ? 3 : 2) * a.Nout;
-        atomicAdd(st + qq * a.Nout + n, sum);
+        atomicAdd(stat_slab(a.stats, EPI >= 1 ? 3 : 2, a.Nout) + qq * a.Nout + n, sum);
     }
 }
 

@@ -39,6 +39,7 @@
 
 #include <cstdlib>
 
+#include "conv_epilogue.h"
 #include "conv_igemm_impl.h"
 
 namespace {
@@ -93,6 +94,67 @@ constexpr int stream_gtp(int mode) { return mode >= 6 ? 64 : 0; }  // P of the T
 __device__ __forceinline__ int gt_hswz(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
 __device__ __forceinline__ int gt_gswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }  // image (b), 16-B chunks
 
+// accumulator fragments -> the wave-private swizzled tile (rows of `pitch` bytes): pixel fr, channels i * 16 + 4 fq
+// .. + 3 per lane. DS instructions of one wave execute in order: the row-chunk re-reads (epi_read) see these writes,
+// and the previous group's reads are complete (their results were consumed) before these writes land.
+template <int FN>
+__device__ __forceinline__ void frags_to_tile(char* sE, int pitch, int fr, int fq, const f32x4 (&acc)[FN]) {
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+        *reinterpret_cast<u32x2*>(sE + fr * pitch + epi_swz(fr, (i * 16 + fq * 4) * 2)) =
+            u32x2{pack_bf2(acc[i][0], acc[i][1]), pack_bf2(acc[i][2], acc[i][3])};
+    __builtin_amdgcn_wave_barrier();
+}
+
+// MODE 5's next-conv stage of one group: Y2 rows = (the 16 x BN tile of stored bits in sE) x W2^T. B fragment of k-step
+// ks = chunk ks * 4 + fq of pixel row fr; the second output goes through the same wave-private tile (every fragment
+// read is complete by then: the accumulators depend on them) as 16 x CO2 bf16, rows of CO2 * 2 bytes, and leaves as
+// coalesced 16-B row chunks with its shifted forward statistics (shift2 / s1 / s2 of the lane's chunk lane % (CO2 / 8))
+template <int BN, int CO2>
+__device__ __forceinline__ void next_conv_stage(const IGemmArgs& a, char* sE, const char* sW2, const int (&aoff2)[4],
+                                                int g, int ngroups, int lane, const float (&shift2)[8],
+                                                float (&s1)[8], float (&s2)[8]) {
+    constexpr int EP = BN * 2, RB2 = BN * 2, FN2 = CO2 / 16, EP2 = CO2 * 2, CH2 = CO2 / 8, PPR2 = 64 / CH2;
+    const int fr = lane & 15, fq = lane >> 4;
+    bf16x8 fb2[BN / 32];
+#pragma unroll
+    for (int ks = 0; ks < BN / 32; ++ks) fb2[ks] = __builtin_bit_cast(bf16x8, epi_read(sE, fr, EP, ks * 4 + fq));
+    f32x4 acc2[FN2];
+#pragma unroll
+    for (int i = 0; i < FN2; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // MFMA t = (k-step t / FN2, channel fragment t % FN2); W2 fragments through a ring of RR2 registers read RR2 - 1
+    // MFMAs ahead, as the main GEMM's (see there for the group barriers)
+    constexpr int NT2 = (BN / 32) * FN2, RR2 = 8;
+    auto w2frag = [&](int t) {
+        return *reinterpret_cast<const bf16x8*>(sW2 + (t % FN2) * 16 * RB2 + aoff2[(t / FN2) & 3] +
+                                                ((t / FN2) >> 2) * 256);
+    };
+    bf16x8 fa2[RR2];
+#pragma unroll
+    for (int t = 0; t < RR2 - 1; ++t) fa2[t] = w2frag(t);
+    __builtin_amdgcn_sched_group_barrier(0x100, RR2 - 1, 0);
+#pragma unroll
+    for (int t = 0; t < NT2; ++t) {
+        if (t + RR2 - 1 < NT2) {
+            fa2[(t + RR2 - 1) % RR2] = w2frag(t + RR2 - 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        acc2[t % FN2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa2[t % RR2], fb2[t / FN2], acc2[t % FN2], 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+    }
+    frags_to_tile<FN2>(sE, EP2, fr, fq, acc2);
+    const __amdgpu_buffer_rsrc_t ry2 = buf_rsrc(a.Y2 + (size_t)(g < ngroups ? g * 16 : 0) * CO2, true);
+#pragma unroll
+    for (int q = 0; q < 16 / PPR2; ++q) {
+        const int p = q * PPR2 + lane / CH2, c2 = lane % CH2;
+        const bool ev2 = g < ngroups && g * 16 + p < a.M;
+        const u32x4 t = epi_read(sE, p, EP2, c2);
+        __builtin_amdgcn_raw_buffer_store_b128(t, ry2, ev2 ? (uint32_t)(p * CO2 + c2 * 8) * 2 : BUF_OOB, 0, 0);
+        if (a.stats2) stat_fwd(t, ev2 ? 1.f : 0.f, shift2, s1, s2);  // shifted sums, as the plain epilogue's
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <int K, int BN, int D, int MODE, bool STEM = false, bool XBN = false, int K2 = 0>
 __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(const IGemmArgs a) {
     constexpr int NW = stream_nw(MODE), CO2 = stream_co2(MODE);
@@ -114,8 +176,7 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
     constexpr bool FO = MODE == 4 || MODE == 5, NX = MODE == 5;
     static_assert(!GT || (BN == 128 && P == 64 && K2 == 0 && !STEM && !XBN), "T modes: 128-channel slices, p = 64");
     constexpr int RB2 = BN * 2;        // W2 row pitch in LDS (bytes): BN / 8 chunks, swizzled in groups of 16
-    constexpr int FN2 = CO2 / 16;      // channel fragments of the second output
-    constexpr int EP2 = CO2 * 2, CH2 = NX ? CO2 / 8 : 1, PPR2 = 64 / CH2, NR2 = NX ? 16 / PPR2 : 0;
+    constexpr int CH2 = NX ? CO2 / 8 : 1;  // 16-B chunks per pixel of the second output
     static_assert(!NX || (K2 == 0 && !STEM && !XBN && BN == 256 && (CO2 == 64 || CO2 == 128)), "next-conv mode");
     static_assert(NX || CO2 == 0, "CO2: next-conv mode only");
     // chunks whose global reads are batched; with the BN-backward epilogue all
@@ -152,7 +213,9 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
         }
     }
 
-    // fixed epilogue channel chunk of this lane + the BN constants it needs
+    // fixed epilogue channel chunk of this lane + the BN constants it needs. (This kernel's main epilogue -- constants,
+    // chunk arithmetic, final fold -- stays written out: each of the three, moved onto shared helpers, put a
+    // 255 / 256-VGPR instantiation into scratch, profiles/conv_epilogue_refactor.md)
     const int cc = lane % CH;
     const int n = n0 + cc * 8;
     float mean[8], rstd[8], sc[8], sh[8], m2[8], r2[8];
@@ -353,17 +416,10 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
     float xsc[XBN ? KS : 1][8], xsh[XBN ? KS : 1][8];  // this lane's channels ks * 32 + fq * 8 + e
     if constexpr (XBN) {
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x4 sc4 = *reinterpret_cast<const f32x4*>(a.xbn + ks * 32 + fq * 8 + 4 * h);
-                const f32x4 sh4 = *reinterpret_cast<const f32x4*>(a.xbn + a.C + ks * 32 + fq * 8 + 4 * h);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    xsc[ks][4 * h + r] = sc4[r];
-                    xsh[ks][4 * h + r] = sh4[r];
-                }
-            }
+        for (int ks = 0; ks < KS; ++ks) {
+            load8(a.xbn, ks * 32 + fq * 8, xsc[ks]);
+            load8(a.xbn, a.C + ks * 32 + fq * 8, xsh[ks]);
+        }
     }
 
     // (GT) T accumulators: rows n0 + wid * 16 + fq * 4 + i, columns jf * 16 + fr
@@ -386,16 +442,9 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
             bf16x8 fb[KS];
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                if constexpr (XBN) {  // BN apply + ReLU on the operand (rows past M are never stored)
-                    u32x4 w = pf[d][ks];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        w[k] = pack_bf2(fmaxf(fmaf(lo_bf(w[k]), xsc[ks][2 * k], xsh[ks][2 * k]), 0.f),
-                                        fmaxf(fmaf(hi_bf(w[k]), xsc[ks][2 * k + 1], xsh[ks][2 * k + 1]), 0.f));
-                    fb[ks] = __builtin_bit_cast(bf16x8, w);
-                } else {
-                    fb[ks] = __builtin_bit_cast(bf16x8, pf[d][ks]);
-                }
+                // (XBN: BN apply + ReLU on the operand; rows past M are never stored)
+                if constexpr (XBN) fb[ks] = __builtin_bit_cast(bf16x8, xbn_apply(pf[d][ks], xsc[ks], xsh[ks]));
+                else fb[ks] = __builtin_bit_cast(bf16x8, pf[d][ks]);
             }
             // the group's epilogue operands: wave-uniform bases at the group's pixel row, per-lane byte offsets
             // (rows past M: out of range, loads read zeros and stores are dropped). Every load of the loop body is
@@ -449,6 +498,8 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
             f32x4 acc[FN];
 #pragma unroll
             for (int i = 0; i < FN; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            // (ring loop and tile write of the main GEMM stay written out here: as one helper shared with the second
+            // GEMM <128, 128, 2, 4> measured +1.9 % and <256, 128, 2, 4> +1.1 % in-step, profiles/conv_epilogue_refactor.md)
             // weight fragments through a ring of RR registers, read RR - 1 MFMAs ahead of use, MFMA t = (k-step
             // t / FN, channel fragment t % FN) (the group barriers pin the interleave: left to itself the scheduler
             // issued each ds_read right before its MFMA and waited for it, a full LDS latency per MFMA)
@@ -595,63 +646,15 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
             if constexpr (NX) {
                 // (the epilogue operands' registers are free again: the next group's go out under the second GEMM)
                 if constexpr (EPF) issue_early(d, g + D * wstride);
-                // the next conv on the tile just stored: B fragment of k-step ks = chunk ks * 4 + fq of pixel row fr
-                bf16x8 fb2[BN / 32];
-#pragma unroll
-                for (int ks = 0; ks < BN / 32; ++ks)
-                    fb2[ks] = __builtin_bit_cast(bf16x8, epi_read(sE, fr, EP, ks * 4 + fq));
-                f32x4 acc2[FN2];
-#pragma unroll
-                for (int i = 0; i < FN2; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                constexpr int NT2 = (BN / 32) * FN2, RR2 = 8;
-                auto w2frag = [&](int t) {  // MFMA t = (k-step t / FN2, channel fragment t % FN2)
-                    return *reinterpret_cast<const bf16x8*>(sW2 + (t % FN2) * 16 * RB2 + aoff2[(t / FN2) & 3] +
-                                                            ((t / FN2) >> 2) * 256);
-                };
-                bf16x8 fa2[RR2];
-#pragma unroll
-                for (int t = 0; t < RR2 - 1; ++t) fa2[t] = w2frag(t);
-                __builtin_amdgcn_sched_group_barrier(0x100, RR2 - 1, 0);
-#pragma unroll
-                for (int t = 0; t < NT2; ++t) {
-                    if (t + RR2 - 1 < NT2) {
-                        fa2[(t + RR2 - 1) % RR2] = w2frag(t + RR2 - 1);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    acc2[t % FN2] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa2[t % RR2], fb2[t / FN2], acc2[t % FN2], 0, 0, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                }
-                // second output through the same wave-private tile (every fb2 read above is complete: the
-                // accumulators depend on them): 16 x CO2 bf16, rows of EP2 bytes, then coalesced 16-B row chunks
-#pragma unroll
-                for (int i = 0; i < FN2; ++i)
-                    *reinterpret_cast<u32x2*>(sE + fr * EP2 + epi_swz(fr, (i * 16 + fq * 4) * 2)) =
-                        u32x2{pack_bf2(acc2[i][0], acc2[i][1]), pack_bf2(acc2[i][2], acc2[i][3])};
-                __builtin_amdgcn_wave_barrier();
-                const __amdgpu_buffer_rsrc_t ry2 = buf_rsrc(a.Y2 + (size_t)(g < ngroups ? g * 16 : 0) * CO2, true);
-#pragma unroll
-                for (int q = 0; q < NR2; ++q) {
-                    const int p = q * PPR2 + lane / CH2, c2 = lane % CH2;
-                    const bool ev2 = g < ngroups && g * 16 + p < a.M;
-                    const u32x4 t = epi_read(sE, p, EP2, c2);
-                    __builtin_amdgcn_raw_buffer_store_b128(t, ry2, ev2 ? (uint32_t)(p * CO2 + c2 * 8) * 2 : BUF_OOB, 0, 0);
-                    if (a.stats2) {  // shifted sums of the stored values, as the plain epilogue's
-                        const float vf = ev2 ? 1.f : 0.f;
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) {
-                            const float v = (c & 1 ? hi_bf(t[c >> 1]) : lo_bf(t[c >> 1])) * vf;
-                            const float dd = (v - mean[c]) * vf;
-                            s1[c] += dd;
-                            s2[c] += dd * dd;
-                        }
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
+                next_conv_stage<BN, CO2>(a, sE, sW2, aoff2, g, ngroups, lane, mean, s1, s2);
             }
             if constexpr (EPF && !NX) issue_early(d, g + D * wstride);
             if constexpr (GT) {
                 static_assert(!GT || !EPF, "T modes: the epilogue operands are issued at the group's start");
+                // The T stage of one round. INVARIANT: it holds a block barrier (and another one sits before the tiles
+                // are written again), so every wave of the block runs the same number of rounds -- the group loop runs on
+                // the block's first group index, and groups past the end are all out of range. (Written out: as a
+                // function the three T-mode kernels measured +0.3 .. +1.6 % in-step, profiles/conv_epilogue_refactor.md)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int hr = j * 8 + (lane >> 3);
@@ -684,23 +687,12 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
         m8 = wave_max(m8);
         if (lane == 0) atomic_max_pos(a.y8amax + (blockIdx.x & 31), m8);
     }
+    // fold the lanes that share a channel chunk, one atomic per channel and quantity
     if constexpr (NX) {  // the second output's statistics (the first has none in this mode)
         if (!a.stats2) return;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-#pragma unroll
-            for (int o = CH2; o < 64; o <<= 1) {
-                s1[c] += __shfl_xor(s1[c], o, 64);
-                s2[c] += __shfl_xor(s2[c], o, 64);
-            }
-        }
-        if (lane >= CH2) return;
-        float* st2 = a.stats2 + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 2 * CO2 + lane * 8;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            atomicAdd(st2 + c, s1[c]);
-            atomicAdd(st2 + CO2 + c, s2[c]);
-        }
+        float* st2 = stat_slab(a.stats2, 2, CO2) + (lane % CH2) * 8;
+        flush_chunk_lanes<CH2>(s1, st2, lane);
+        flush_chunk_lanes<CH2>(s2, st2 + CO2, lane);
         return;
     }
     if (!a.stats) return;
@@ -715,7 +707,7 @@ __global__ __launch_bounds__(stream_nw(MODE) * 64, 2) void conv_stream_kernel(co
         }
     }
     if (lane >= CH) return;
-    float* st = a.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * (bnb ? 3 : 2) * a.Nout;
+    float* st = stat_slab(a.stats, bnb ? 3 : 2, a.Nout);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         if constexpr (!GT) atomicAdd(st + n + c, s1[c]);
@@ -794,13 +786,11 @@ __global__ __launch_bounds__(256, 2) void stem_band_kernel(const IGemmArgs a, in
     const int cc = lane & 7, n = cc * 8;
     const bool affine = a.flags & IG_AFFINE, relu = a.flags & IG_RELU;
     float mean[8], sc[8], sh[8], s1[8], s2[8];
+    load8(a.stats && a.shift, a.shift, n, mean);
+    load8(affine, a.bias, n, sc, 1.f);
+    load8(affine, a.bias, a.Nout + n, sh);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        mean[c] = (a.stats && a.shift) ? a.shift[n + c] : 0.f;
-        sc[c] = affine ? a.bias[n + c] : 1.f;
-        sh[c] = affine ? a.bias[a.Nout + n + c] : 0.f;
-        s1[c] = s2[c] = 0.f;
-    }
+    for (int c = 0; c < 8; ++c) s1[c] = s2[c] = 0.f;
 
     u32x4 stage[CPT];
     auto load_band = [&](int band) {  // global -> registers
@@ -857,12 +847,8 @@ __global__ __launch_bounds__(256, 2) void stem_band_kernel(const IGemmArgs a, in
                 for (int i = 0; i < FN; ++i)
                     acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[ks][i], fb, acc[i], 0, 0, 0);
             }
-            // (1) fragments -> wave-private LDS rows (pixel fr, channels i * 16 + 4 fq .. + 3), swizzled
-#pragma unroll
-            for (int i = 0; i < FN; ++i)
-                *reinterpret_cast<u32x2*>(sE + fr * EP + epi_swz(fr, (i * 16 + fq * 4) * 2)) =
-                    u32x2{pack_bf2(acc[i][0], acc[i][1]), pack_bf2(acc[i][2], acc[i][3])};
-            __builtin_amdgcn_wave_barrier();
+            // (1) fragments -> wave-private LDS rows
+            frags_to_tile<FN>(sE, EP, fr, fq, acc);
             // (2) row chunks: pixel q * 8 + lane / 8, channels n .. n + 7
             const long m0 = ((long)img * a.OH + oy0 + ry) * a.OW + ox0;
 #pragma unroll
@@ -879,17 +865,10 @@ __global__ __launch_bounds__(256, 2) void stem_band_kernel(const IGemmArgs a, in
                         v[2 * k + 1] = fmaxf(v[2 * k + 1], 0.f);
                     }
                 }
-                u32x4 o;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = pack_bf2(v[2 * k], v[2 * k + 1]);
+                const u32x4 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
                 *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(a.Y) + (m0 + p) * a.ldy + n) = o;
-                if (a.stats) {
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {  // statistics of the stored (bf16) values
-                        const float d = (c & 1 ? hi_bf(o[c >> 1]) : lo_bf(o[c >> 1])) - mean[c];
-                        s1[c] += d;
-                        s2[c] += d * d;
-                    }
+                if (a.stats) {  // (a band holds whole rows: every pixel counts)
+                    stat_fwd(o, 1.f, mean, s1, s2);
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -901,21 +880,9 @@ __global__ __launch_bounds__(256, 2) void stem_band_kernel(const IGemmArgs a, in
         buf ^= 1;
     }
     if (!a.stats) return;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-#pragma unroll
-        for (int o = 8; o < 64; o <<= 1) {
-            s1[c] += __shfl_xor(s1[c], o, 64);
-            s2[c] += __shfl_xor(s2[c], o, 64);
-        }
-    }
-    if (lane >= 8) return;
-    float* st = a.stats + (size_t)(blockIdx.x & (STAT_SLOTS - 1)) * 2 * a.Nout;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        atomicAdd(st + n + c, s1[c]);
-        atomicAdd(st + a.Nout + n + c, s2[c]);
-    }
+    float* st = stat_slab(a.stats, 2, a.Nout) + n;
+    flush_chunk_lanes<8>(s1, st, lane);
+    flush_chunk_lanes<8>(s2, st + a.Nout, lane);
 }
 
 template <int R>

@@ -112,15 +112,16 @@ def test_fwd_stream_slices(shape, tile, epi):
     _fwd_tile(shape, tile, epi)
 
 
-def test_fwd_halo():
-    """The halo-tiled 64 -> 64 3x3 (conv_halo.hip), the default dispatch at this shape."""
+@pytest.mark.parametrize("shape", [(3, 64, 56, 64, 3, 1, 1), (1, 64, 112, 64, 3, 1, 1)], ids=_id)
+def test_fwd_halo(shape):
+    """The halo-tiled 64 -> 64 3x3 (conv_halo.hip), the default dispatch at these shapes: halo3x3_kernel<56, 4> and
+    <112, 2> (layer 1 of a 448-pixel input)."""
     from imagent_amd.ops.conv import igemm_fwd
-    shape = (3, 64, 56, 64, 3, 1, 1)
     x, w, ref = _fwd_case(shape)
     slab = _slab(64)
     y, names = kernel_names(lambda: igemm_fwd(x, w, 1, 1, 3, 3, stats=slab))
     print(f"fwd {shape}: {short_names(names)}")
-    assert any("halo3x3_kernel" in n for n in names), names
+    assert any(f"halo3x3_kernel<{shape[2]}, " in n for n in names), names
     _check_fwd(y, slab, ref)
 
 

@@ -28,7 +28,7 @@ import torch
 
 from exact_ref import (DYADIC, abs_sums, assert_bf16_exact, assert_out_exact, assert_sums_exact, bn_consts, bnb_ref,
                        bnb_terms, dgrad_ref, dyadic, e4m3_ref, fused_out_ref, fwd_ref, halves, ints, kernel_names,
-                       mask_bytes, out_size, shifted_stats_ref, short_names, ternary, ternary_density)
+                       mask_bytes, out_size, shifted_stats_ref, short_names, stem_form, ternary, ternary_density)
 
 pytestmark = pytest.mark.gpu
 
@@ -167,29 +167,46 @@ def test_fused_output(kc, size, res_scale, q8):
         assert a8.max().item() == amax, (a8.max().item(), amax)
 
 
+HALO112 = (1, 64, 112, 64, 3, 1, 1)  # halo3x3_kernel<112, 2, EPI>: layer 1 of a 448-pixel input
+STEM = (2, 4, 224, 64, 7, 2, 3)      # the 224-px 7x7 / 2 stem in stem_form
 EVAL = [("conv_stream", (5, 64, 13, 256, 1, 1, 0), 0, 0), ("conv_stream", (5, 128, 13, 512, 1, 1, 0), 0, 0),
         ("conv_stream", (5, 256, 13, 512, 1, 1, 0), 0, 0), ("conv_stream", "big", 0, 0),
         ("halo3x3", (3, 64, 56, 64, 3, 1, 1), 0, 0)] + \
        [("igemm", (7, 64, 14, 128, 3, 1, 1), t, e) for t in (2, 4, 8) for e in (0, 1, 2)] + \
-       [("igemm", (7, 64, 14, 128, 3, 1, 1), 18, e) for e in (0, 2)]  # (the v3 loop has the staged epilogue only)
+       [("igemm", (7, 64, 14, 128, 3, 1, 1), 18, e) for e in (0, 2)] + \
+       [("halo3x3_kernel<112, 2, 0>", HALO112, 0, 0), ("stem_band_kernel<4>", STEM, 0, 0),
+        ("conv_stream", STEM, 23, 0)]  # (tile 18: the v3 loop has the staged epilogue only)
+EVAL_IDS = [f"{f.split('<')[0]}-{_id(s)}-t{t}-e{e}" for f, s, t, e in EVAL]
+# Nonzero density of the added cases (the others: ternary_density(K)). The output relu(y * sc + sh) with |sc| <= 2 and
+# half-integer sh is a multiple of 0.5, exact in bf16 below 128, so |y| <= 62 is needed. Halo K = 576 at d = 0.35:
+# y has variance 71, 62 = 7.4 sigma (at 0.5: 5.2 sigma of 8e5 elements). Stem K = 147 at d = 0.5: variance 37, 10 sigma
+EVAL_DENSITY = {HALO112: 0.35, STEM: 0.5}
 
 
-@pytest.mark.parametrize("family,shape,tile,epi", EVAL, ids=[f"{f}-{_id(s)}-t{t}-e{e}" for f, s, t, e in EVAL])
+@pytest.mark.parametrize("family,shape,tile,epi", EVAL, ids=EVAL_IDS)
 def test_eval_affine_relu(family, shape, tile, epi):
-    """affine + relu alone (the eval epilogue) on the streaming, tiled (direct / staged) and halo kernels."""
+    """affine + relu alone (the eval epilogue) on the streaming, tiled (direct / staged), halo and stem kernels."""
     from imagent_amd.ops.conv import igemm_fwd
     big = shape == "big"
     if big:
         shape = (_big(1)[0], 64, 14, 256, 1, 1, 0)
     N, Ci, H, Co, k, s, p = shape
-    d = ternary_density(k * k * Ci)
+    stem = shape == STEM
+    d = EVAL_DENSITY.get(shape, ternary_density(k * k * Ci))
     x, w = ternary((N, H, H, Ci), d, 1, DEV), ternary((Co, k, k, Ci), d, 2, DEV)
+    wk = w
+    if stem:  # channel 3 zero, [Co][KH][32] weight rows
+        x, w = stem_form(x), stem_form(w)
+        wk = torch.zeros(Co, k, 32, dtype=torch.bfloat16, device=DEV)
+        wk[:, :, :k * Ci] = w.reshape(Co, k, k * Ci)
     aff = torch.stack([dyadic(Co, 10, DYADIC, DEV), halves(Co, -2, 2, 11, DEV)]).contiguous()
-    y, names = _launch(lambda: kernel_names(lambda: igemm_fwd(x, w, s, p, k, k, affine=aff, relu=True, tile=tile,
-                                                              epi=epi)))
+    y, names = _launch(lambda: kernel_names(lambda: igemm_fwd(x, wk, s, p, k, k, affine=aff, relu=True, tile=tile,
+                                                              epi=epi, stem=stem)))
     print(f"eval {shape} tile {tile} epi {epi}: {short_names(names)}")
     assert names and all(family in n for n in names), names
-    if family == "conv_stream":
+    if stem and family == "conv_stream":
+        assert _stream_args(names) == [(224, 64, 2, 0)], names
+    elif family == "conv_stream":
         _check_geometry(N * H * H, Co, names, "big" if big else "ragged", mode=0)
     zeros = 0
     for sl in _chunks(N, H * H):
@@ -354,13 +371,16 @@ def test_stride2_dgrad_bnb(variant):
     _bnb_check(o, shape, got)
 
 
-@pytest.mark.parametrize("variant", VARIANTS)
-def test_halo_dgrad_bnb(variant):
-    shape = (3, 64, 56, 64, 3, 1, 1)
+HALO_BNB = [((3, 64, 56, 64, 3, 1, 1), v) for v in VARIANTS] + [(HALO112, v) for v in VARIANTS]
+
+
+@pytest.mark.parametrize("shape,variant", HALO_BNB, ids=[v if s[2] == 56 else f"{v}-w{s[2]}" for s, v in HALO_BNB])
+def test_halo_dgrad_bnb(shape, variant):
+    """halo3x3_kernel<56, 4, EPI> and <112, 2, EPI> (EPI 1, with x2: 2)."""
     o = _bnb_operands(shape, variant)
     got, names = _bnb_run(o, shape)
     print(f"bnb dgrad {shape} {variant}: {short_names(names)}")
-    assert names and all("halo3x3_kernel" in n for n in names), names
+    assert names and all(f"halo3x3_kernel<{shape[2]}, " in n for n in names), names
     _bnb_check(o, shape, got)
 
 
