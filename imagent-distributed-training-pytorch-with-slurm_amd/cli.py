@@ -78,6 +78,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--source-size", type=int, default=None, metavar="N",
                    help="--data imagenet: the size the JPEG folder loader decodes to (default --image-size), so that "
                         "--random-resized-crop has pixels to crop from; records and synthetic data hold their own")
+    p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                   help="Mixup train augmentation: every sample becomes lam x + (1 - lam) x' with a partner x' of its "
+                        "batch, lam ~ Beta(ALPHA, ALPHA), and the loss is taken against both labels (one HIP kernel "
+                        "for the batch, one pair of loss kernels; validation never mixes). 0: off. Cost at 4096 img: "
+                        "profiles/mix_pairs.md")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                   help="CutMix train augmentation: a box of the partner, sqrt(1 - lam) of each side around a uniform "
+                        "centre, is pasted into the sample, lam ~ Beta(ALPHA, ALPHA) then set to the share of pixels "
+                        "kept. 0: off. With --mixup too, each mixed sample is one or the other (--mix-switch-prob)")
+    p.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
+                   help="--mixup / --cutmix: the probability that a sample is mixed at all")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="P",
+                   help="--mixup and --cutmix together: the probability that a mixed sample is CutMix")
     # --- optimisation ---
     p.add_argument("--optimizer", default="sgd",
                    choices=["sgd", "lars", "adam", "adamw", "adagrad", "rmsprop", "adadelta", "asgd", "nadam"])

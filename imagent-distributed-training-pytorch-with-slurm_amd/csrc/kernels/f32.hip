@@ -1210,3 +1210,34 @@ IMK_EXPORT int imk_xent_bwd_f32(const float* logits, const int64_t* labels, cons
     IMK_CHECK_LAUNCH();
     return 0;
 }
+
+// the two-label form (misc.hip xent_pair_bwd_kernel) with an fp32 gradient
+namespace {
+__global__ __launch_bounds__(256) void xent_pair_bwd_f32_kernel(const float* __restrict__ logits,
+                                                                const int64_t* __restrict__ ya,
+                                                                const int64_t* __restrict__ yb,
+                                                                const float* __restrict__ lam,
+                                                                const float* __restrict__ lse,
+                                                                const float* __restrict__ gout,
+                                                                float* __restrict__ dz, int B, int NC,
+                                                                float smoothing) {
+    const int row = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= NC) return;
+    const float scale = gout[0] / (float)B;
+    const float p = expf(logits[(size_t)row * NC + i] - lse[row]);
+    const float l = lam[row];
+    const float w = (i == ya[row] ? l : 0.f) + (i == yb[row] ? 1.f - l : 0.f);
+    const float t = (1.f - smoothing) * w + smoothing / (float)NC;
+    dz[(size_t)row * NC + i] = (p - t) * scale;
+}
+}  // namespace
+
+IMK_EXPORT int imk_xent_pair_bwd_f32(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                                     const float* lse, const float* gout, float* dz, int B, int NC, float smoothing,
+                                     void* stream) {
+    hipLaunchKernelGGL(xent_pair_bwd_f32_kernel, dim3((NC + 255) / 256, B), dim3(256), 0, (hipStream_t)stream,
+                       logits, ya, yb, lam, lse, gout, dz, B, NC, smoothing);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}

@@ -12,7 +12,9 @@
 //           -> normalize_u8 (uint8 HWC -> bf16 NHWC, optional crop / flip)
 //   K13     fc bias gradient -> colsum_bf16
 //   -       bf16 weight shadows: [Co][T][Ci] -> [Ci][T][Co] for dgrad (batched)
+//   -       Mixup / CutMix (no reference counterpart): mix_pairs, the two-label xent_pair_fwd / xent_pair_bwd
 
+#include <algorithm>
 #include <cstdlib>
 #include <vector>
 
@@ -556,6 +558,76 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
     dz[(size_t)row * NC + i] = f2bf((p - t) * scale);
 }
 
+// The two-label form (Mixup / CutMix, data/mix.py): row b's target is
+//   t = (1 - eps) (lam[b] 1[ya[b]] + (1 - lam[b]) 1[yb[b]]) + eps / NC,
+// its loss (1 - eps) (lam (lse - z[ya]) + (1 - lam) (lse - z[yb])) + eps (lse - sum z / NC). Top-1 / top-5 count
+// against the label with the larger weight (ya when lam >= 0.5). The reductions are xent_fwd_kernel's, in its
+// order: lam == 1 gives its lse bit for bit.
+__global__ __launch_bounds__(256) void xent_pair_fwd_kernel(const float* __restrict__ logits,
+                                                            const int64_t* __restrict__ ya,
+                                                            const int64_t* __restrict__ yb,
+                                                            const float* __restrict__ lam,
+                                                            float* __restrict__ lse_out,
+                                                            float* __restrict__ loss_mean,
+                                                            float* __restrict__ metrics, int B, int NC,
+                                                            float smoothing) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    const float* z = logits + (size_t)row * NC;
+    const int64_t la = ya[row], lb = yb[row];
+    const float l = lam[row];
+    float mx = -INFINITY;
+    for (int i = lane; i < NC; i += 64) mx = fmaxf(mx, z[i]);
+    mx = wave_max(mx);
+    float se = 0.f, sz = 0.f;
+    for (int i = lane; i < NC; i += 64) {
+        se += expf(z[i] - mx);
+        sz += z[i];
+    }
+    se = wave_sum(se);
+    sz = wave_sum(sz);
+    const float lse = mx + logf(se);
+    const float za = (la >= 0 && la < NC) ? z[la] : 0.f;
+    const float zb = (lb >= 0 && lb < NC) ? z[lb] : 0.f;
+    const float zd = l >= 0.5f ? za : zb;  // the dominant label's logit: its rank is what top-k counts
+    int gt = 0;
+    for (int i = lane; i < NC; i += 64) gt += z[i] > zd;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gt += __shfl_xor(gt, o, 64);
+    if (lane == 0) {
+        const float nll = l * (lse - za) + (1.f - l) * (lse - zb);
+        const float loss = (1.f - smoothing) * nll + smoothing * (lse - sz / (float)NC);
+        lse_out[row] = lse;
+        atomicAdd(loss_mean, loss / (float)B);
+        if (metrics) {
+            atomicAdd(metrics + 0, loss);
+            atomicAdd(metrics + 1, gt < 1 ? 1.f : 0.f);
+            atomicAdd(metrics + 2, gt < 5 ? 1.f : 0.f);
+            atomicAdd(metrics + 3, 1.f);
+        }
+    }
+}
+
+// dlogits = g/B * (softmax - t), t as above; bf16 out as xent_bwd_kernel
+__global__ __launch_bounds__(256) void xent_pair_bwd_kernel(const float* __restrict__ logits,
+                                                            const int64_t* __restrict__ ya,
+                                                            const int64_t* __restrict__ yb,
+                                                            const float* __restrict__ lam,
+                                                            const float* __restrict__ lse,
+                                                            const float* __restrict__ gout,
+                                                            bf16_t* __restrict__ dz, int B, int NC,
+                                                            float smoothing) {
+    const int row = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= NC) return;
+    const float scale = gout[0] / (float)B;
+    const float p = __expf(logits[(size_t)row * NC + i] - lse[row]);
+    const float l = lam[row];
+    const float w = (i == ya[row] ? l : 0.f) + (i == yb[row] ? 1.f - l : 0.f);
+    const float t = (1.f - smoothing) * w + smoothing / (float)NC;
+    dz[(size_t)row * NC + i] = f2bf((p - t) * scale);
+}
+
 // out[c] += sum_r x[r][c]. Block = 64 columns x 4 row lanes, blockIdx.y = a
 // slice of rows: every thread sums a few rows (one column per thread, 128-B
 // coalesced row segments per wave), the 4 row lanes fold in LDS and one
@@ -1005,6 +1077,134 @@ static void rrc_config(int Hs, int H, int W, int* band, int* lds_bytes) {
     *lds_bytes = (int)(need < cap ? (need < 1024 ? 1024 : need) : cap);
 }
 
+// ------------------------------------------------------------ Mixup / CutMix
+// out[b] from x[b] and its partner x[pair[b]] (x, out: NHWC [B][H][W][CP], bf16 or fp32; out of place -- a partner
+// may be a sample this launch also rewrites). boxes[b] = (top, left, h, w):
+//   a box with h, w > 0 (CutMix): out = the partner inside the box, x[b] outside -- a select, bit for bit;
+//   an empty box (Mixup): out = round(lam[b] x[b] + (1 - lam[b]) partner) in fp32; lam 1 / 0 copy x[b] / the
+//   partner bit for bit (a sample that is not mixed is lam 1 with an empty box).
+// A pure HBM stream. A sample is a flat run of VB-byte vectors (VB 16; 8 where a sample's bytes or a pointer are
+// no multiple of 16: bf16 at CP 4 with H W odd), cut into chunks of 256 x MIX_U vectors. A block takes chunks
+// grid-stride, so pair / lam / box are block-uniform (scalar loads) and the kind of sample is a uniform branch;
+// every thread issues its MIX_U loads before the first use. A box sample loads each vector from the one source it
+// needs: only where VB holds two pixels (bf16, CP 4) can a vector straddle a box edge, and only those load the
+// other source too -- about 1 read + 1 write per CutMix sample, 2 reads + 1 write per Mixup sample, 1 + 1 for a
+// copy. Offsets: size_t per sample and chunk, 32 bits inside a chunk; a pixel's index in its sample fits 32 bits
+// (the launcher checks H W < 2^31). pair is clamped into the batch and the box only enters comparisons, so no
+// value of either reads or writes out of bounds.
+constexpr int MIX_U = 4;
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <int VB> struct MixVec;
+template <> struct MixVec<16> { typedef u32x4 type; };
+template <> struct MixVec<8> { typedef u32x2 type; };
+
+template <typename T>
+__device__ __forceinline__ uint32_t mix_word(uint32_t a, uint32_t p, float l, float m) {
+    if (std::is_same<T, float>::value) return __float_as_uint(l * __uint_as_float(a) + m * __uint_as_float(p));
+    return pack_bf2(l * lo_bf(a) + m * lo_bf(p), l * hi_bf(a) + m * hi_bf(p));
+}
+
+template <typename T, int VB, int CP>
+__global__ __launch_bounds__(256) void mix_pairs_kernel(const T* __restrict__ x, T* __restrict__ out,
+                                                        const int* __restrict__ pair, const float* __restrict__ lam,
+                                                        const int* __restrict__ boxes, int B, int W, size_t sample,
+                                                        uint32_t chunks, long items) {
+    typedef typename MixVec<VB>::type V;
+    constexpr int EPV = VB / (int)sizeof(T), NW = VB / 4, CHE = 256 * MIX_U * EPV;
+    constexpr bool TWO = EPV > CP;  // a vector holds two pixels: words [0, NW / 2) the first, the rest the second
+    // item = b chunks + c walks on by the grid size without a division per chunk; the next chunk's pair / lam / box
+    // are asked for before this chunk's vectors, so their scalar loads are not in front of every chunk's stream
+    const uint32_t sb = gridDim.x / chunks, sc = gridDim.x % chunks;
+    uint32_t b = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    int pr_n = pair[b];
+    float l_n = lam[b];
+    i32x4 box_n = *reinterpret_cast<const i32x4*>(boxes + 4 * (size_t)b);
+#pragma unroll 1
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t bc = b, cc = c;
+        const int pr = min(max(pr_n, 0), B - 1);
+        const float l = l_n;
+        const int top = box_n[0], left = box_n[1], bh = box_n[2], bw = box_n[3];
+        c += sc;
+        b += sb + (c >= chunks ? 1 : 0);
+        c -= c >= chunks ? chunks : 0;
+        const uint32_t bn = min(b, (uint32_t)B - 1);  // (past the last chunk: any sample, never used)
+        pr_n = pair[bn];
+        l_n = lam[bn];
+        box_n = *reinterpret_cast<const i32x4*>(boxes + 4 * (size_t)bn);
+        const size_t e0 = (size_t)cc * CHE;                                 // the chunk's first element in its sample
+        const uint32_t ne = (uint32_t)min((size_t)CHE, sample - e0);        // and how many it holds
+        const T* xa = x + (size_t)bc * sample + e0;
+        const T* xp = x + (size_t)pr * sample + e0;
+        T* o = out + (size_t)bc * sample + e0;
+        // Loads are never predicated: a lane past the chunk's end (the last chunk of a sample) loads the chunk's last
+        // vector instead, and only its store is skipped. A load under a divergent branch would make the compiler
+        // wait for every load in flight around it (common.h, the note at BUF_OOB).
+        uint32_t off[MIX_U], ld[MIX_U];
+#pragma unroll
+        for (int k = 0; k < MIX_U; ++k) {
+            off[k] = (uint32_t)(k * 256 + threadIdx.x) * EPV;
+            ld[k] = min(off[k], ne - EPV);
+        }
+        V v[MIX_U];
+        if (bh > 0 && bw > 0) {
+            const uint32_t pix0 = (uint32_t)(e0 / CP);
+            bool in1[MIX_U], straddle[MIX_U];
+#pragma unroll
+            for (int k = 0; k < MIX_U; ++k) {
+                const uint32_t pix = pix0 + ld[k] / CP;
+                const int row = (int)(pix / (uint32_t)W), col = (int)(pix - (uint32_t)row * (uint32_t)W);
+                const bool in0 = row >= top && row < top + bh && col >= left && col < left + bw;
+                in1[k] = in0;
+                if (TWO) {
+                    const int col1 = col + 1 == W ? 0 : col + 1, row1 = col + 1 == W ? row + 1 : row;
+                    in1[k] = row1 >= top && row1 < top + bh && col1 >= left && col1 < left + bw;
+                }
+                straddle[k] = in1[k] != in0;
+                v[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>((in0 ? xp : xa) + ld[k]));
+            }
+            if (TWO) {
+#pragma unroll
+                for (int k = 0; k < MIX_U; ++k)
+                    if (straddle[k]) {  // a box edge between the vector's two pixels: the second from the other source
+                        const V w = *reinterpret_cast<const V*>((in1[k] ? xp : xa) + ld[k]);
+#pragma unroll
+                        for (int j = NW / 2; j < NW; ++j) v[k][j] = w[j];
+                    }
+            }
+        } else if (l == 1.f || l == 0.f) {
+            const T* s = l == 1.f ? xa : xp;
+#pragma unroll
+            for (int k = 0; k < MIX_U; ++k) v[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(s + ld[k]));
+        } else {
+            const float m = 1.f - l;
+            V u[MIX_U];
+#pragma unroll
+            for (int k = 0; k < MIX_U; ++k) {
+                v[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(xa + ld[k]));
+                u[k] = __builtin_nontemporal_load(reinterpret_cast<const V*>(xp + ld[k]));
+            }
+#pragma unroll
+            for (int k = 0; k < MIX_U; ++k)
+#pragma unroll
+                for (int j = 0; j < NW; ++j) v[k][j] = mix_word<T>(v[k][j], u[k][j], l, m);
+        }
+#pragma unroll
+        for (int k = 0; k < MIX_U; ++k)
+            if (off[k] < ne) __builtin_nontemporal_store(v[k], reinterpret_cast<V*>(o + off[k]));
+    }
+}
+
+// blocks per CU of mix_pairs_kernel's grid (IMAGENT_MIX_BPC: A/B in one process, read on every call). As the 2-in
+// 1-out stream of profiles/hbm_roof.md it is fastest at 2: at 4096 img, 2 / 4 / 8 / 16 blocks per CU take 885 / 907 /
+// 935 / 922 us all-Mixup, 584 / 617 / 622 / 613 us as a plain copy, 664 / 647 / 663 / 654 us all-CutMix (whose
+// index arithmetic likes more waves) -- profiles/mix_pairs.md
+static int mix_bpc() {
+    const char* e = getenv("IMAGENT_MIX_BPC");
+    return e && *e ? min(max(atoi(e), 1), 32) : 2;
+}
+
 // ------------------------------------------------- batched weight transposes
 // dst[ci][t][co] = src[co][t][ci]  for every conv in the descriptor table.
 struct TDesc {
@@ -1169,6 +1369,26 @@ IMK_EXPORT int imk_xent_bwd(const float* logits, const int64_t* labels, const fl
     return 0;
 }
 
+// the two-label loss (xent_pair_fwd_kernel): ya, yb int64 [B], lam float [B]
+IMK_EXPORT int imk_xent_pair_fwd(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                                 float* lse, float* loss_mean, float* metrics, int B, int NC, float smoothing,
+                                 void* stream) {
+    if (hipMemsetAsync(loss_mean, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) return -1;
+    hipLaunchKernelGGL(xent_pair_fwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, ya, yb,
+                       lam, lse, loss_mean, metrics, B, NC, smoothing);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
+IMK_EXPORT int imk_xent_pair_bwd(const float* logits, const int64_t* ya, const int64_t* yb, const float* lam,
+                                 const float* lse, const float* gout, void* dz, int B, int NC, float smoothing,
+                                 void* stream) {
+    hipLaunchKernelGGL(xent_pair_bwd_kernel, dim3((NC + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, logits,
+                       ya, yb, lam, lse, gout, (bf16_t*)dz, B, NC, smoothing);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
 // The stem's weight gradient from its row-segment layout gp [Co][KH][32] (channel-padded 4-channel pixels, kw * 4 +
 // ci) into the master gradient, stored [Co][KH][KW][Ci] in the arena (+=, gradient accumulation), clearing gp for
 // the next step's atomic accumulation in the same pass (one launch instead of a fill + a strided add).
@@ -1315,6 +1535,37 @@ IMK_EXPORT int imk_rrc_normalize_u8(const void* in, void* out, const int* boxes,
         else IMK_RRC(bf16_t, 0, 1);
     }
 #undef IMK_RRC
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
+// Mixup / CutMix of a batch with itself (mix_pairs_kernel): x, out bf16 (is_f32 0) or fp32 (1) NHWC [B][H][W][Cp],
+// Cp 4 or 8, out != x; pair int32 [B], lam float [B], boxes int32 [B][4] on the device
+IMK_EXPORT int imk_mix_pairs(const void* x, void* out, const int* pair, const float* lam, const int* boxes, int B,
+                             int H, int W, int Cp, int is_f32, void* stream) {
+    if (B < 0 || H < 1 || W < 1 || !x || !out || x == out || !pair || !lam || !boxes) return -1;
+    if (Cp != 4 && Cp != 8) return -100;
+    if ((long)H * W >= (1L << 31)) return -101;  // a pixel's index in its sample: 32 bits
+    if (B == 0) return 0;
+    const size_t es = is_f32 ? 4 : 2, sample = (size_t)H * W * Cp;
+    const size_t al = (size_t)(uintptr_t)x | (size_t)(uintptr_t)out | (sample * es);
+    const int vb = al % 16 == 0 ? 16 : al % 8 == 0 ? 8 : 0;
+    if (!vb) return -100;
+    const size_t che = (size_t)256 * MIX_U * (vb / es);
+    const uint32_t chunks = (uint32_t)((sample + che - 1) / che);
+    const long items = (long)B * chunks;
+    const dim3 g((uint32_t)std::min(items, (long)device_cus() * mix_bpc())), bl(256);
+#define IMK_MIX(T, VB, CP)                                                                                          \
+    hipLaunchKernelGGL((mix_pairs_kernel<T, VB, CP>), g, bl, 0, (hipStream_t)stream, (const T*)x, (T*)out, pair,    \
+                       lam, boxes, B, W, sample, chunks, items)
+    if (is_f32) {
+        if (vb == 16) { if (Cp == 4) IMK_MIX(float, 16, 4); else IMK_MIX(float, 16, 8); }
+        else { if (Cp == 4) IMK_MIX(float, 8, 4); else IMK_MIX(float, 8, 8); }
+    } else {
+        if (vb == 16) { if (Cp == 4) IMK_MIX(bf16_t, 16, 4); else IMK_MIX(bf16_t, 16, 8); }
+        else { if (Cp == 4) IMK_MIX(bf16_t, 8, 4); else IMK_MIX(bf16_t, 8, 8); }
+    }
+#undef IMK_MIX
     IMK_CHECK_LAUNCH();
     return 0;
 }

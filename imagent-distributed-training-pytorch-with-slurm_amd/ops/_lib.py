@@ -170,6 +170,7 @@ def _declare(name: str, lib) -> None:
             "imk_colsum_f32": [vp, vp, i32, i32, vp],
             "imk_normalize_u8_f32": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
             "imk_xent_bwd_f32": [vp, vp, vp, vp, vp, i32, i32, f32, vp],
+            "imk_xent_pair_bwd_f32": [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp],
             "imk_bn_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, i32, vp, vp, vp,
                            vp, vp, vp, vp, vp, i32, vp],
             "imk_bn_bwd": [vp] * 17 + [i64, i32, i32, i32, vp],
@@ -190,6 +191,8 @@ def _declare(name: str, lib) -> None:
             "imk_avgpool_bwd": [vp, vp, i32, i32, i32, vp],
             "imk_xent_fwd": [vp, vp, vp, vp, vp, i32, i32, f32, vp],
             "imk_xent_bwd": [vp, vp, vp, vp, vp, i32, i32, f32, vp],
+            "imk_xent_pair_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp],
+            "imk_xent_pair_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp],
             "imk_colsum_bf16": [vp, vp, i32, i32, vp],
             "imk_stem_grad_fold": [vp, vp, i32, i32, i32, i32, vp],
             "imk_memset0": [vp, i64, vp],
@@ -209,6 +212,7 @@ def _declare(name: str, lib) -> None:
             "imk_normalize_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
             "imk_resize_normalize_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
             "imk_rrc_normalize_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
+            "imk_mix_pairs": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
             "imk_transpose_batched": [vp, i32, i32, vp],
             "imk_stream_create_cumask": [i32, C.POINTER(vp)],
             "imk_igemm_args_size": [], "imk_wgrad_args_size": [], "imk_bn_rundesc_size": [], "imk_bn_affdesc_size": [],

@@ -233,6 +233,44 @@ class XentFn(torch.autograd.Function):
         return dz, None, None, None
 
 
+class XentPairFn(torch.autograd.Function):
+    """The two-label form of :class:`XentFn` for Mixup / CutMix batches (``data/mix.py``): row b's target is
+    ``(1 - eps) (lam[b] 1[ya[b]] + (1 - lam[b]) 1[yb[b]]) + eps / NC``; top-1 / top-5 count against the label with
+    the larger weight (``ya`` when ``lam >= 0.5``). ``lam == 1`` gives ``XentFn`` on ``ya`` (``lse`` and the
+    gradient bit for bit). ``ya`` / ``yb`` int64 [B], ``lam`` float32 [B]. One Function for the bf16 and the fp32
+    kernel path: the gradient kernel follows the logits' dtype, as ``XentFn.backward``."""
+
+    @staticmethod
+    def forward(ctx, logits, ya, yb, lam, metrics, smoothing):
+        logits = logits.contiguous()
+        B, NC = logits.shape
+        if ya.shape != (B,) or yb.shape != (B,) or lam.shape != (B,):
+            raise ValueError(f"XentPairFn: ya {tuple(ya.shape)}, yb {tuple(yb.shape)}, lam {tuple(lam.shape)} for "
+                             f"{B} rows")
+        ya, yb = ya.to(torch.int64).contiguous(), yb.to(torch.int64).contiguous()
+        lam = lam.to(torch.float32).contiguous()
+        lse = torch.empty(B, device=logits.device, dtype=torch.float32)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)  # cleared by imk_xent_pair_fwd
+        _lib.check(_lib.kernels().imk_xent_pair_fwd(logits.data_ptr(), ya.data_ptr(), yb.data_ptr(), lam.data_ptr(),
+                                                    lse.data_ptr(), loss.data_ptr(), _lib.ptr(metrics), B, NC,
+                                                    float(smoothing), _lib.stream_ptr()), "xent pair")
+        ctx.save_for_backward(logits, ya, yb, lam, lse)
+        ctx.smoothing = smoothing
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, ya, yb, lam, lse = ctx.saved_tensors
+        B, NC = logits.shape
+        g = gout.to(torch.float32).contiguous()
+        dz = torch.empty((B, NC), device=logits.device, dtype=logits.dtype)  # (XentFn.backward on the dtype)
+        k = _lib.kernels()
+        fn = k.imk_xent_pair_bwd_f32 if logits.dtype == torch.float32 else k.imk_xent_pair_bwd
+        _lib.check(fn(logits.data_ptr(), ya.data_ptr(), yb.data_ptr(), lam.data_ptr(), lse.data_ptr(), g.data_ptr(),
+                      dz.data_ptr(), B, NC, float(ctx.smoothing), _lib.stream_ptr()), "xent pair bwd")
+        return dz, None, None, None, None, None
+
+
 # -------------------------------------------------------------------- SGD
 def sgd_flat(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor],
              shadow: Optional[torch.Tensor], lr: float, momentum: float, dampening: float,
@@ -327,6 +365,42 @@ def rrc_normalize_u8(images: torch.Tensor, out_hw, cpad: int, mean: Sequence[flo
                                                    B, Hs, Ws, H, W, cpad, C.cast(m, C.c_void_p),
                                                    C.cast(s, C.c_void_p), 1 if out.dtype == torch.float32 else 0,
                                                    _lib.stream_ptr()), "random-resized-crop + normalize")
+    return out
+
+
+def mix_pairs(x: torch.Tensor, pair: torch.Tensor, lam: torch.Tensor, boxes: torch.Tensor,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mixup / CutMix of a batch with itself, one HIP kernel (csrc/kernels/misc.hip mix_pairs_kernel): ``x`` NHWC
+    [B, H, W, Cp] (bf16 or fp32, Cp 4 or 8, as the normalise kernels leave it), ``pair`` int32 [B] the partner of
+    each sample, ``lam`` float32 [B], ``boxes`` int32 [B, 4] = (top, left, h, w). A sample with a non-empty box
+    takes its partner's pixels inside the box (a bit-exact select); one with an empty box becomes
+    ``lam x[b] + (1 - lam) x[pair[b]]`` (fp32 arithmetic, round-to-nearest-even to bf16; ``lam`` 1 / 0 copy bit for
+    bit). Out of place: ``out`` must not alias ``x``. The draws come from ``data/mix.py``; nothing here
+    synchronises with the host."""
+    if x.dim() != 4 or not x.is_contiguous() or x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"mix_pairs: x {tuple(x.shape)} {x.dtype} (contiguous NHWC, bf16 or fp32)")
+    B, H, W, Cp = x.shape
+    if Cp not in (4, 8):
+        raise ValueError(f"mix_pairs: {Cp} channels (the padded 4 or 8 of the model input)")
+    if tuple(pair.shape) != (B,) or tuple(lam.shape) != (B,) or tuple(boxes.shape) != (B, 4):
+        raise ValueError(f"mix_pairs: pair {tuple(pair.shape)}, lam {tuple(lam.shape)}, boxes {tuple(boxes.shape)} "
+                         f"for {B} samples")
+    pair = pair.to(device=x.device, dtype=torch.int32).contiguous()
+    lam = lam.to(device=x.device, dtype=torch.float32).contiguous()
+    boxes = boxes.to(device=x.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        nb = x.numel() * x.element_size()
+        if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or \
+                (out.data_ptr() < x.data_ptr() + nb and x.data_ptr() < out.data_ptr() + nb):
+            raise ValueError("mix_pairs: out must be a contiguous tensor of x's shape and dtype that does not "
+                             "overlap x")
+    if x.numel() == 0:
+        return out
+    _lib.check(_lib.kernels().imk_mix_pairs(x.data_ptr(), out.data_ptr(), pair.data_ptr(), lam.data_ptr(),
+                                            boxes.data_ptr(), B, H, W, Cp, 1 if x.dtype == torch.float32 else 0,
+                                            _lib.stream_ptr()), "mix pairs")
     return out
 
 

@@ -74,7 +74,25 @@ class StepRunner:
         while len(self._inflight) > self.max_inflight:
             self._inflight.popleft().synchronize()
 
+    def _pair_loss(self, logits, ya, yb, lam):
+        """The loss of a Mixup / CutMix batch (data/mix.py): target lam 1[ya] + (1 - lam) 1[yb]; top-1 / top-5 count
+        against the label with the larger weight."""
+        if self.backend in ("hip", "hip_f32"):
+            from ..ops.misc import XentPairFn  # serves both: the gradient kernel follows the logits' dtype
+            loss = XentPairFn.apply(logits, ya, yb, lam, self.metrics.buf, self.smoothing)
+            self.metrics.count_batch()
+            return loss
+        z = logits.float()
+        l = lam.to(z.dtype).unsqueeze(1)
+        soft = l * F.one_hot(ya, z.shape[1]).to(z.dtype) + (1.0 - l) * F.one_hot(yb, z.shape[1]).to(z.dtype)
+        loss = F.cross_entropy(z, soft, label_smoothing=self.smoothing)
+        self.metrics.update_from_logits(z, torch.where(lam >= 0.5, ya, yb), loss)
+        return loss
+
     def loss(self, logits, y):
+        """``y``: the labels, or the ``(ya, yb, lam)`` triple of a mixed batch."""
+        if isinstance(y, (tuple, list)):
+            return self._pair_loss(logits, *y)
         if self.backend in ("hip", "hip_f32"):
             from ..ops.misc import XentFn
             if self.backend == "hip_f32":  # fp32 logits gradient
@@ -257,6 +275,19 @@ class Trainer:
                 and not getattr(a, "record_resize", False):
             raise SystemExit(f"--source-size {ss} is smaller than --image-size {a.image_size}: only "
                              "--random-resized-crop resamples the decoded images")
+        mu, cm = getattr(a, "mixup", 0.0), getattr(a, "cutmix", 0.0)
+        if not (mu >= 0.0):
+            raise SystemExit(f"--mixup {mu}: need ALPHA >= 0 (0: off)")
+        if not (cm >= 0.0):
+            raise SystemExit(f"--cutmix {cm}: need ALPHA >= 0 (0: off)")
+        mp, sp = getattr(a, "mix_prob", 1.0), getattr(a, "mix_switch_prob", 0.5)
+        if not (0.0 <= mp <= 1.0):
+            raise SystemExit(f"--mix-prob {mp}: need 0 <= P <= 1")
+        if not (0.0 <= sp <= 1.0):
+            raise SystemExit(f"--mix-switch-prob {sp}: need 0 <= P <= 1")
+        if (mu > 0.0 or cm > 0.0) and getattr(a, "hip_graph", False):
+            raise SystemExit("--mixup / --cutmix with --hip-graph: the per-batch draws are not fed into a captured "
+                             "step")
 
     def _build_data(self):
         a = self.args
@@ -337,11 +368,23 @@ class Trainer:
         if center is not None:
             _master_print(self.is_master, "Validation: centre crop {:g} of each side -> {}x{}, antialiased"
                           .format(center, *size))
+        # Mixup / CutMix of every training micro-batch with itself (data/mix.py); validation never mixes
+        self.mixer = None
+        mu, cm = getattr(a, "mixup", 0.0), getattr(a, "cutmix", 0.0)
+        if mu > 0.0 or cm > 0.0:
+            from ..data.mix import BatchMixer
+            self.mixer = BatchMixer(self.kernels, mu, cm, a.mix_prob, a.mix_switch_prob, seed=a.seed, rank=rk)
+            kinds = " / ".join(k for k, al in ((f"Mixup alpha {mu:g}", mu), (f"CutMix alpha {cm:g}", cm)) if al > 0.0)
+            switch = f", CutMix with probability {a.mix_switch_prob:g}" if mu > 0.0 and cm > 0.0 else ""
+            _master_print(self.is_master, f"Augmentation: {kinds}, applied with probability {a.mix_prob:g}{switch}; "
+                                          "two-label loss")
 
     def _loaders(self, epoch: int):
         a = self.args
         self.train_sampler.set_epoch(epoch)   # imagenet.py:375 (val sampler stays at epoch 0)
         self.transform_train.set_epoch(epoch)  # the epoch's RandomResizedCrop boxes and flips (a resume repeats them)
+        if self.mixer is not None:
+            self.mixer.set_epoch(epoch)  # and its Mixup / CutMix draws
         if a.data == "synthetic":
             nt = self.train_sampler.num_batches(a.batch_size)
             nv = self.val_sampler.num_batches(a.batch_size)
@@ -471,6 +514,8 @@ class Trainer:
                 break
             data_wait += time.perf_counter() - tw
             data_time.update(time.perf_counter() - tw)
+            if self.mixer is not None:  # on the current stream: y becomes the (ya, yb, lam) triple
+                x, y = self.mixer(x, y)
             micro.append((x, y))
             if len(micro) < accum:
                 continue
