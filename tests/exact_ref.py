@@ -264,3 +264,197 @@ def kernel_names(fn):
 
 def short_names(names):
     return sorted({n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0] for n in names})
+
+
+# ---- the stand-alone BatchNorm passes (csrc/kernels/bn.hip; tests/test_bn_exact_gpu.py)
+#
+# A pass's per-element work is a handful of fp32 operations on bf16 inputs and per-channel fp32 constants, then one
+# rounding to bf16. The references below are the definitions in fp64; `assert_rounded` allows that one rounding of a
+# value within `delta` of the reference, with `delta` a few fp32 ulps of the sum of the magnitudes of the terms
+# (`bn_fwd_delta`, `bn_bwd_delta`; validated against an fp32 evaluation in the kernels' operation order on every
+# operand set the GPU tests use: tests/test_exact_ref.py). The backward runs on the dyadic operands above, so its
+# masks and sums are exact; the forward has a real rsqrt and runs on Gaussian x.
+
+BN_U = 4  # rows per thread per loop iteration (bn.hip U)
+BN_CS = (8, 24, 64, 1000, 2048)  # cpr = C / 8 chunks per row, rpb = 256 // cpr rows per block iteration
+BN_GRID_R = 3 * 4096 + 3  # C = 2048 (rpb = 1): above 2048 * U (forward grid), 1024 * U (reduce), 4 * CUs * U (apply)
+# the margins' constant: 8 fp32 ulps of the sum of magnitudes. Measured worst |fp32 evaluation - fp64| / margin over
+# every operand set of the GPU tests (test_exact_ref.py::test_bn_margins_hold_for_fp32_evaluation): forward 0.439,
+# backward 0.327 -- inside with the required factor 2, so the constant is not raised
+BN_ULPS = 2.0 ** -21
+
+
+def bn_rpb(C):
+    return 256 // (C // 8)
+
+
+def bn_rows(C):
+    """The row counts of one C: fewer rows than one block holds, exactly one full block iteration, one more row (a
+    second block whose loads all clamp to R - 1), and a tail in the middle of the u loop."""
+    rpb = bn_rpb(C)
+    return (1 if C == 2048 else 3, BN_U * rpb, BN_U * rpb + 1, 3 * BN_U * rpb - rpb + 1)
+
+
+def bf16_spacing(ref):
+    """The distance between neighbouring bf16 values at |ref| (fp64): 2^(floor(log2 |ref|) - 7), and the smallest
+    subnormal 2^-133 below the smallest normal (and at 0)."""
+    _, e = torch.frexp(ref.double().abs())  # |ref| = m 2^e, m in [0.5, 1): floor(log2 |ref|) = e - 1
+    e = torch.where(ref == 0, torch.full_like(e, -1000), e)
+    return torch.ldexp(torch.ones_like(ref, dtype=torch.float64), (e - 8).clamp_min(-133))
+
+
+def assert_rounded(out, ref, delta, what="output"):
+    """Every element of ``out`` is within half a bf16 spacing (at the reference) plus ``delta`` of the fp64 ``ref``:
+    one correct rounding to bf16 of a value within ``delta`` of the reference, and nothing more."""
+    assert out.shape == ref.shape, (out.shape, ref.shape)
+    err = (out.double() - ref).abs()
+    bad = ~(err <= bf16_spacing(ref) / 2 + delta)  # (a NaN is bad)
+    n = bad.sum().item()
+    if n:
+        i = tuple(bad.nonzero()[0].tolist())
+        raise AssertionError(f"{what}: {n} of {ref.numel()} elements off by more than one bf16 rounding, first at "
+                             f"{list(i)}: got {out[i].item()!r}, reference {ref[i].item()!r}, |error| "
+                             f"{err[i].item():.3e}")
+
+
+def _affine(x, mean, rstd, gamma, beta):
+    return (x.double() - mean.double()) * rstd.double() * gamma.double() + beta.double()
+
+
+def bn_fwd_ref(x, mean, var, gamma, beta, eps, mode, relu, x2=None, mean2=None, var2=None, gamma2=None, beta2=None):
+    """act((x - mean) / sqrt(var + eps) * gamma + beta [+ x2 | + the same of branch 2]) in fp64:
+    (output, pre-activation, rstd[, rstd2])."""
+    rstd = 1.0 / torch.sqrt(var.double() + eps)
+    pre = _affine(x, mean, rstd, gamma, beta)
+    out = [rstd]
+    if mode == 1:
+        pre = pre + x2.double()
+    elif mode == 2:
+        rstd2 = 1.0 / torch.sqrt(var2.double() + eps)
+        pre = pre + _affine(x2, mean2, rstd2, gamma2, beta2)
+        out.append(rstd2)
+    return (pre.clamp_min(0) if relu else pre, pre, *out)
+
+
+def bn_fwd_delta(x, mean, var, gamma, beta, eps, mode, x2=None, mean2=None, var2=None, gamma2=None, beta2=None):
+    """The forward's margin: BN_ULPS * (|x sc| + |mean sc| + |beta| [+ |res|] [+ the same of branch 2]), sc = gamma *
+    rstd in fp64 -- var + eps and the rsqrt (2 ulps), rstd * gamma (1), beta - mean * k (2), the FMA (1), the branch
+    add (1 or 2)."""
+    sc = gamma.double() / torch.sqrt(var.double() + eps)
+    d = (x.double() * sc).abs() + (mean.double() * sc).abs() + beta.double().abs()
+    if mode == 1:
+        d = d + x2.double().abs()
+    elif mode == 2:
+        sc2 = gamma2.double() / torch.sqrt(var2.double() + eps)
+        d = d + (x2.double() * sc2).abs() + (mean2.double() * sc2).abs() + beta2.double().abs()
+    return BN_ULPS * d
+
+
+def bn_bwd_ref(dy, x, save, gamma, beta, mode, mask, y=None, x2=None, save2=None, gamma2=None):
+    """The BatchNorm backward in fp64, the formulas of the kernel comments: the gradient masked by ``mask`` (None,
+    "y": y > 0, "x": x sc + sh > 0 with sc = gamma rstd, sh = beta - mean sc), Sg = sum gm, Sgx = sum gm xhat with
+    xhat = (x - mean) rstd, dx = gamma rstd (gm - Sg / R - xhat Sgx / R); mode 1: dres = gm; mode 2: Sgx2 and dx2
+    over branch 2 (x2, save2, gamma2), dbeta2 = Sg. Keys that a mode does not produce are None."""
+    C = x.shape[-1]
+    R = x.numel() // C
+    mean, rstd, gam = save[0].double(), save[1].double(), gamma.double()
+    xd, gm = x.double(), dy.double()
+    if mask == "y":
+        gm = gm * (y.double() > 0)
+    elif mask == "x":
+        sc = gam * rstd
+        gm = gm * (xd * sc + (beta.double() - mean * sc) > 0)
+    else:
+        assert mask is None, mask
+    xhat = (xd - mean) * rstd
+    Sgx, Sg = (gm * xhat).reshape(-1, C).sum(0), gm.reshape(-1, C).sum(0)
+    out = dict(gm=gm, Sgx=Sgx, Sg=Sg, Sgx2=torch.zeros_like(Sg), dx=gam * rstd * (gm - Sg / R - xhat * Sgx / R),
+               dres=gm if mode == 1 else None, dx2=None, dgamma=Sgx, dbeta=Sg, dgamma2=None, dbeta2=None)
+    if mode == 2:
+        mean2, rstd2 = save2[0].double(), save2[1].double()
+        xhat2 = (x2.double() - mean2) * rstd2
+        Sgx2 = (gm * xhat2).reshape(-1, C).sum(0)
+        out.update(Sgx2=Sgx2, dgamma2=Sgx2, dbeta2=Sg, dx2=gamma2.double() * rstd2 * (gm - Sg / R - xhat2 * Sgx2 / R))
+    return out
+
+
+def bn_bwd_delta(gm, x, save, gamma, Sgx, Sg):
+    """The backward's margin for dx = k1 g + kx x + k0 (k1 = gamma rstd, kx = -k1 rstd Sgx / R, k0 = -k1 Sg / R - kx
+    mean): BN_ULPS * (|k1 g| + |kx x| + |kx mean| + |k1 Sg / R|), in fp64. dx2: the same with branch 2's x2, save2,
+    gamma2 and Sgx2."""
+    R = x.numel() // x.shape[-1]
+    mean, rstd = save[0].double(), save[1].double()
+    k1 = gamma.double() * rstd
+    kx = -k1 * rstd * Sgx / R
+    return BN_ULPS * ((k1 * gm).abs() + (kx * x.double()).abs() + (kx * mean).abs() + (k1 * Sg / R).abs())
+
+
+class Operands(dict):
+    """A dict with attribute access; ``to(device)`` moves every tensor."""
+    __getattr__ = dict.__getitem__
+
+    def to(self, device):
+        return Operands({k: v.to(device) if torch.is_tensor(v) else v for k, v in self.items()})
+
+
+def bn_bwd_operands(C, R, seed=0):
+    """The backward's dyadic operand set [R][C] (CPU; the same values wherever it is used): g integers in [-3, 3], x
+    and x2 integers in [-4, 4], `bn_consts` for both branches, and the bf16 forward outputs y0 / y1 / y2 of modes
+    0 / 1 / 2 (with ReLU) that the mask-from-y cases read."""
+    s = 1000 * seed
+    o = Operands(C=C, R=R, g=ints((R, C), -3, 3, s + 1), x=ints((R, C), -4, 4, s + 2), x2=ints((R, C), -4, 4, s + 3))
+    o["save"], o["gamma"], o["beta"] = bn_consts(C, s + 10)
+    o["save2"], o["gamma2"], o["beta2"] = bn_consts(C, s + 20)
+    a = _affine(o.x, o.save[0], o.save[1], o.gamma, o.beta)
+    o["y0"] = a.clamp_min(0).to(torch.bfloat16)
+    o["y1"] = (a + o.x2.double()).clamp_min(0).to(torch.bfloat16)
+    o["y2"] = (a + _affine(o.x2, o.save2[0], o.save2[1], o.gamma2, o.beta2)).clamp_min(0).to(torch.bfloat16)
+    return o
+
+
+def bn_bwd_case_ref(o, mode, mask):
+    """(`bn_bwd_ref` of the operand set ``o`` for one mode and mask, after its exactness preconditions; delta of dx;
+    delta of dx2 or None)."""
+    ref = bn_bwd_ref(o.g, o.x, o.save, o.gamma, o.beta, mode, mask, y=o["y%d" % mode] if mask == "y" else None,
+                     x2=o.x2 if mode == 2 else None, save2=o.save2, gamma2=o.gamma2)
+    assert_sums_exact(bnb_terms(ref["gm"], o.x, o.save, o.x2 if mode == 2 else None, o.save2), 0.25)
+    d = bn_bwd_delta(ref["gm"], o.x, o.save, o.gamma, ref["Sgx"], ref["Sg"])
+    d2 = bn_bwd_delta(ref["gm"], o.x2, o.save2, o.gamma2, ref["Sgx2"], ref["Sg"]) if mode == 2 else None
+    return ref, d, d2
+
+
+def bn_fwd_operands(C, R, seed=0):
+    """The forward's operand set [R][C] (CPU): Gaussian x (scale 2, offset 0.5), integer x2 in [-4, 4] (the residual
+    or branch 2's input), random means, positive variances in [0.05, 4], gammas of both signs in +-[0.5, 1.5] and
+    betas for both branches."""
+    g = _gen(2000 * seed + 7, "cpu")
+
+    def rn(*shape):
+        return torch.randn(*shape, generator=g)
+
+    o = Operands(C=C, R=R, eps=1e-5, x=(rn(R, C) * 2 + 0.5).to(torch.bfloat16), x2=ints((R, C), -4, 4, 2000 * seed + 8))
+    for k in ("", "2"):
+        o["mean" + k] = rn(C) * 0.5 + (0.5 if k == "" else 0.0)
+        o["var" + k] = torch.rand(C, generator=g) * 3.95 + 0.05
+        sign = torch.randint(0, 2, (C,), generator=g).float() * 2 - 1
+        o["gamma" + k] = sign * (torch.rand(C, generator=g) + 0.5)
+        o["beta" + k] = rn(C) * 0.5
+    return o
+
+
+def bn_fwd_case_ref(o, mode, relu):
+    """(`bn_fwd_ref` of the operand set ``o``, `bn_fwd_delta`)."""
+    kw = dict(x2=o.x2, mean2=o.mean2, var2=o.var2, gamma2=o.gamma2, beta2=o.beta2) if mode else {}
+    return (bn_fwd_ref(o.x, o.mean, o.var, o.gamma, o.beta, o.eps, mode, relu, **kw),
+            bn_fwd_delta(o.x, o.mean, o.var, o.gamma, o.beta, o.eps, mode, **kw))
+
+
+def split_slots(total, slots, quantum, seed, spread=64):
+    """[slots][...] fp32 pieces, each a multiple of ``quantum`` of magnitude <= spread * quantum except the last,
+    that add up to ``total`` (fp64, on the quantum grid) exactly: a slab whose fold is known."""
+    g = _gen(seed, "cpu")
+    k = torch.randint(-spread, spread + 1, (slots - 1, *total.shape), generator=g).double().to(total.device) * quantum
+    last = total.double() - k.sum(0)
+    out = torch.cat([k, last[None]]).float()
+    assert torch.equal(out.double().sum(0), total.double()), "pieces do not add up exactly in fp32"
+    return out
