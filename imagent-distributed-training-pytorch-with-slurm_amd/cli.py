@@ -106,6 +106,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scale-lr", action="store_true", help="lr *= global_batch / 256")
     p.add_argument("--label-smoothing", type=float, default=0.0)
     p.add_argument("--accum-steps", type=int, default=1, help="gradient accumulation micro-batches")
+    p.add_argument("--model-ema", type=float, default=0.0, metavar="DECAY",
+                   help="keep an exponential moving average of the weights, E += (1 - DECAY) (p - E) once per "
+                        "optimizer step, and of the BatchNorm running statistics; every epoch validates the raw "
+                        "weights and then the average (EMA Test lines, val_ema TensorBoard series), and --save-model "
+                        "also writes the best average as imagenet_FR_<arch>_ema.pt. Two elementwise HIP launches per "
+                        "step after the optimizer's. 0: off; else 0 < DECAY < 1 (e.g. 0.9999). Cost: "
+                        "profiles/model_ema.md")
+    p.add_argument("--model-ema-warmup", action="store_true",
+                   help="--model-ema: ramp the decay as min(DECAY, (1 + t) / (10 + t)) over the t updates done, so "
+                        "the average forgets the initial weights quickly (not with --hip-graph: a per-step kernel "
+                        "argument would re-capture every step)")
     # --- parallelism / runtime ---
     p.add_argument("--launcher", default="auto", choices=["auto", "slurm", "torchrun", "single"])
     p.add_argument("--kernels", default="auto", choices=["auto", "hip", "torch"],

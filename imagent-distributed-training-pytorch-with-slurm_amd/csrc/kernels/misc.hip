@@ -688,6 +688,51 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     }
 }
 
+// --model-ema (train/ema.py): the weight average e += omd * (p - e) over the flat arena, omd = 1 - decay (the lerp
+// form: e == p is a fixed point), after the optimizer's step. A launch of its own: fused into sgd_kernel it measured
+// no faster than the two launches (profiles/model_ema.md), so there is no fused kernel.
+__global__ __launch_bounds__(256) void ema_flat_kernel(float* __restrict__ e, const float* __restrict__ p, long n,
+                                                       float omd) {
+    const long n4 = n / 4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4 + (n % 4 ? 1 : 0);
+         i += (long)gridDim.x * 256) {
+        if (i < n4) {
+            f32x4 ev = reinterpret_cast<f32x4*>(e)[i];
+            const f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ev[j] += omd * (pv[j] - ev[j]);
+            reinterpret_cast<f32x4*>(e)[i] = ev;
+        } else {
+            for (long k = n4 * 4; k < n; ++k) e[k] += omd * (p[k] - e[k]);
+        }
+    }
+}
+
+// p <-> e in place, shadow = bf16(new p): the evaluation of the averaged weights swaps them in and out again
+// (two swaps restore every bit; the pointers every descriptor table holds do not move).
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ e,
+                                                       bf16_t* __restrict__ shadow, long n) {
+    const long n4 = n / 4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4 + (n % 4 ? 1 : 0);
+         i += (long)gridDim.x * 256) {
+        if (i < n4) {
+            const f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+            const f32x4 ev = reinterpret_cast<f32x4*>(e)[i];
+            reinterpret_cast<f32x4*>(p)[i] = ev;
+            reinterpret_cast<f32x4*>(e)[i] = pv;
+            if (shadow)
+                reinterpret_cast<u32x2*>(shadow)[i] = u32x2{pack_bf2(ev[0], ev[1]), pack_bf2(ev[2], ev[3])};
+        } else {
+            for (long k = n4 * 4; k < n; ++k) {
+                const float pv = p[k], ev = e[k];
+                p[k] = ev;
+                e[k] = pv;
+                if (shadow) shadow[k] = f2bf(ev);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ p,
                                                         bf16_t* __restrict__ o, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) o[i] = f2bf(p[i]);
@@ -1452,6 +1497,23 @@ IMK_EXPORT int imk_sgd(float* p, const float* g, float* buf, void* shadow, long 
                        float damp, float wd, int nesterov, int first, float gs, void* stream) {
     hipLaunchKernelGGL(sgd_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p,
                        g, buf, (bf16_t*)shadow, n, lr, mu, damp, wd, nesterov, first, gs);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
+IMK_EXPORT int imk_ema_flat(float* e, const float* p, long n, float omd, void* stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(ema_flat_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, e, p, n,
+                       omd);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
+// shadow may be null (the fp32 path keeps no bf16 copy)
+IMK_EXPORT int imk_ema_swap(float* p, float* e, void* shadow, long n, void* stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(stream_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, e,
+                       (bf16_t*)shadow, n);
     IMK_CHECK_LAUNCH();
     return 0;
 }

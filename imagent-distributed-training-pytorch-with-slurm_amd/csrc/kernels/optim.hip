@@ -88,3 +88,55 @@ IMK_EXPORT int imk_lars_step(const void* descs, int T, long max_n, float* norms,
 }
 
 IMK_EXPORT int imk_lars_desc_size() { return (int)sizeof(LarsDesc); }
+
+// ------------------------------------------------------------------------------------------------------------
+// The weight average's side of the model buffers (--model-ema, train/ema.py): every float buffer (BatchNorm
+// running_mean / running_var) has its average in one flat fp32 side buffer. One launch over a per-tensor
+// descriptor table, blockIdx.y = tensor, serves all of them:
+//   mode 0 (EMA):   flat[off + i] += omd * (buf[i] - flat[off + i])
+//   mode 1 (swap):  buf[i] <-> flat[off + i], in place: the running-statistics and eval-affine descriptor tables
+//                   and the cross-rank buffer broadcast hold the buffers' own storage, so no pointer may move.
+struct EmaBufDesc {
+    float* buf;  // the model's buffer
+    long off;    // its offset in the flat side buffer, in floats
+    long n;
+};
+
+namespace {
+
+template <bool SWAP>
+__global__ __launch_bounds__(256) void ema_bufs_kernel(const EmaBufDesc* __restrict__ d, float* __restrict__ flat,
+                                                       float omd) {
+    const EmaBufDesc q = d[blockIdx.y];
+    float* __restrict__ a = flat + q.off;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < q.n; i += (long)gridDim.x * 256) {
+        const float b = q.buf[i], e = a[i];
+        if constexpr (SWAP) {
+            q.buf[i] = e;
+            a[i] = b;
+        } else {
+            a[i] = e + omd * (b - e);
+        }
+    }
+}
+
+}  // namespace
+
+// descs: device array of T EmaBufDesc; flat: the side buffer they index; mode 0: EMA with omd, 1: swap
+IMK_EXPORT int imk_ema_bufs(const void* descs, int T, long max_n, float* flat, float omd, int mode, void* stream) {
+    if (T <= 0) return 0;
+    if (T > 65535 || (mode != 0 && mode != 1)) return -100;
+    long bx = (max_n + 255) / 256;
+    if (bx > 64) bx = 64;
+    if (bx < 1) bx = 1;
+    if (mode == 1)
+        hipLaunchKernelGGL(ema_bufs_kernel<true>, dim3((int)bx, T), dim3(256), 0, (hipStream_t)stream,
+                           (const EmaBufDesc*)descs, flat, omd);
+    else
+        hipLaunchKernelGGL(ema_bufs_kernel<false>, dim3((int)bx, T), dim3(256), 0, (hipStream_t)stream,
+                           (const EmaBufDesc*)descs, flat, omd);
+    IMK_CHECK_LAUNCH();
+    return 0;
+}
+
+IMK_EXPORT int imk_ema_bufdesc_size() { return (int)sizeof(EmaBufDesc); }

@@ -104,6 +104,11 @@ class LarsDesc(C.Structure):
                 ("n", C.c_long), ("adapt", C.c_int), ("pad", C.c_int)]
 
 
+class EmaBufDesc(C.Structure):
+    """optim.hip EmaBufDesc: one model buffer and where its average lies in the flat side buffer (train/ema.py)."""
+    _fields_ = [("buf", C.c_void_p), ("off", C.c_long), ("n", C.c_long)]
+
+
 class QDesc(C.Structure):
     """fp8.hip QDesc: one weight tensor of the per-step e4m3 quantisation."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n4", C.c_long), ("exp", C.c_void_p),
@@ -207,6 +212,10 @@ def _declare(name: str, lib) -> None:
             "imk_bn_gram_wgrad_fixup": [vp, vp, vp, vp, vp, vp, i32, i32, vp],
             "imk_bn_gram_p": [vp, vp, vp, vp, i64, i32, i32, vp],
             "imk_sgd": [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, f32, vp],
+            "imk_ema_flat": [vp, vp, i64, f32, vp],
+            "imk_ema_swap": [vp, vp, vp, i64, vp],
+            "imk_ema_bufs": [vp, i32, i64, vp, f32, i32, vp],
+            "imk_ema_bufdesc_size": [],
             "imk_cast_bf16": [vp, vp, i64, vp],
             "imk_uncast_bf16": [vp, vp, i64, vp],
             "imk_normalize_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
@@ -232,7 +241,8 @@ def _declare(name: str, lib) -> None:
         # ABI guard: the ctypes mirrors must match the compiled structs
         for fn, st in [("imk_igemm_args_size", IGemmArgs), ("imk_wgrad_args_size", WgradArgs),
                        ("imk_bn_rundesc_size", RunDesc), ("imk_bn_affdesc_size", AffDesc), ("imk_tdesc_size", TDesc),
-                       ("imk_qdesc_size", QDesc), ("imk_lars_desc_size", LarsDesc)]:
+                       ("imk_qdesc_size", QDesc), ("imk_lars_desc_size", LarsDesc),
+                       ("imk_ema_bufdesc_size", EmaBufDesc)]:
             n = getattr(lib, fn)()
             if n != C.sizeof(st):
                 raise RuntimeError(f"{fn}: native {n} B != ctypes {C.sizeof(st)} B - rebuild")

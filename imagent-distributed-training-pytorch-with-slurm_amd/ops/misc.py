@@ -281,6 +281,38 @@ def sgd_flat(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor],
                                       _lib.stream_ptr()), "sgd")
 
 
+def ema_flat(e: torch.Tensor, p: torch.Tensor, omd: float) -> None:
+    """``e += omd * (p - e)`` over two flat fp32 arenas of one length."""
+    assert e.numel() == p.numel() and e.dtype == p.dtype == torch.float32
+    assert e.is_contiguous() and p.is_contiguous()
+    _lib.check(_lib.kernels().imk_ema_flat(e.data_ptr(), p.data_ptr(), e.numel(), omd, _lib.stream_ptr()), "ema")
+
+
+def ema_swap(p: torch.Tensor, e: torch.Tensor, shadow: Optional[torch.Tensor]) -> None:
+    """``p <-> e`` in place and ``shadow = bf16(new p)`` (``shadow`` may be None)."""
+    assert e.numel() == p.numel() and e.dtype == p.dtype == torch.float32
+    assert e.is_contiguous() and p.is_contiguous()
+    assert shadow is None or (shadow.numel() == p.numel() and shadow.dtype == torch.bfloat16)
+    _lib.check(_lib.kernels().imk_ema_swap(p.data_ptr(), e.data_ptr(), _lib.ptr(shadow), p.numel(),
+                                           _lib.stream_ptr()), "ema swap")
+
+
+def ema_buf_table(bufs, offsets, device) -> torch.Tensor:
+    """The device descriptor table of :func:`ema_bufs`: buffer ``i`` averages into ``flat[offsets[i]:][:numel]``."""
+    d = (_lib.EmaBufDesc * len(bufs))()
+    for q, b, o in zip(d, bufs, offsets):
+        assert b.dtype == torch.float32 and b.is_contiguous()
+        q.buf, q.off, q.n = b.data_ptr(), o, b.numel()
+    return torch.frombuffer(bytearray(bytes(memoryview(d))), dtype=torch.uint8).to(device)
+
+
+def ema_bufs(table: torch.Tensor, count: int, max_n: int, flat: torch.Tensor, omd: float, swap: bool) -> None:
+    """One launch over ``table`` (:func:`ema_buf_table`): the average of every buffer into ``flat``, or
+    (``swap``) buffer <-> average in place."""
+    _lib.check(_lib.kernels().imk_ema_bufs(table.data_ptr(), count, max_n, flat.data_ptr(), omd, 1 if swap else 0,
+                                           _lib.stream_ptr()), "ema buffers")
+
+
 def cast_bf16(src: torch.Tensor, dst: torch.Tensor) -> None:
     _lib.check(_lib.kernels().imk_cast_bf16(src.data_ptr(), dst.data_ptr(), src.numel(),
                                             _lib.stream_ptr()), "cast")

@@ -313,17 +313,18 @@ class DataParallel(nn.Module):
         self.tracker = _Tracker(bucket_of, nb)
 
     @torch.no_grad()
-    def check_consistency(self, raise_on_mismatch: bool = True) -> bool:
+    def check_consistency(self, raise_on_mismatch: bool = True, extra=()) -> bool:
         """Race / divergence detector: after identical averaged
         gradients every rank must hold bit-identical parameters. A bucket read
         by RCCL before its producing kernel finished, or a compute kernel
         overwriting a bucket during its all-reduce, shows up here as a
-        checksum mismatch. Costs one tiny all-gather; call it every N steps."""
+        checksum mismatch. Costs one tiny all-gather; call it every N steps.
+        ``extra``: further flat tensors that must agree across ranks (the --model-ema weight average)."""
         if self.comm.world_size <= 1:
             return True
-        P = self.arena.P
-        sig = torch.stack([P.double().sum(), (P.double() * torch.arange(P.numel(), device=P.device,
-                                                                         dtype=torch.float64).remainder_(977)).sum()])
+        sig = torch.stack([s for P in (self.arena.P, *extra) for s in (
+            P.double().sum(), (P.double() * torch.arange(P.numel(), device=P.device,
+                                                         dtype=torch.float64).remainder_(977)).sum())])
         allsig = self.comm.allgather(sig)
         ok = bool((allsig == allsig[0]).all())
         if not ok and raise_on_mismatch:

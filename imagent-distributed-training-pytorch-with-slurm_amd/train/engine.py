@@ -218,6 +218,21 @@ class _null:
         return False
 
 
+def apply_relayout(ddp: DataParallel, opt, ema=None, native=None) -> None:
+    """The one-time bucket re-layout, when ``ddp`` has one pending: every arena-shaped tensor moves with the
+    parameters -- the optimizer's momentum and the --model-ema average -- and the native shadows are re-pointed."""
+    if getattr(ddp, "pending_relayout", None) is None:
+        return
+    flats = list(opt.flats())
+    n_opt = len(flats)
+    flats = ddp.apply_pending_relayout(flats + (ema.flats() if ema is not None else []))
+    opt.set_flats(flats[:n_opt])
+    if ema is not None:
+        ema.set_flats(flats[n_opt:])
+    if native:
+        native.rebind()
+
+
 def _abort_c10d() -> None:
     import torch.distributed as dist
     if dist.is_initialized():
@@ -288,6 +303,14 @@ class Trainer:
         if (mu > 0.0 or cm > 0.0) and getattr(a, "hip_graph", False):
             raise SystemExit("--mixup / --cutmix with --hip-graph: the per-batch draws are not fed into a captured "
                              "step")
+        ema, ema_warm = getattr(a, "model_ema", 0.0), getattr(a, "model_ema_warmup", False)
+        if ema != 0.0 and not (0.0 < ema < 1.0):
+            raise SystemExit(f"--model-ema {ema}: need 0 < DECAY < 1 (0: off)")
+        if ema_warm and ema == 0.0:
+            raise SystemExit("--model-ema-warmup needs --model-ema DECAY")
+        if ema_warm and getattr(a, "hip_graph", False):
+            raise SystemExit("--model-ema-warmup with --hip-graph: the decay would be a new kernel argument on every "
+                             "step, and every step a re-capture (a constant --model-ema is captured)")
 
     def _build_data(self):
         a = self.args
@@ -464,8 +487,10 @@ class Trainer:
         if getattr(a, "hip_graph", False):
             if self.device.type != "cuda" or self.ctx.world_size > 1:
                 raise SystemExit("--hip-graph: single-GPU runs only (the RCCL path is not captured)")
+            # (with --model-ema, 1 - decay is a kernel argument like the learning rate)
             self._graph_step = GraphedStep(lambda x, y: self.step.train_step([(x, y)]), warmup=3,
-                                           key_fn=lambda: self.opt.param_groups[0]["lr"])
+                                           key_fn=lambda: self.opt.param_groups[0]["lr"] if self.ema is None else
+                                           (self.opt.param_groups[0]["lr"], self.ema.omd()))
         self.start_epoch = 0
         self.best = dict(top1=0.0, top5=0.0, epoch_top1=0, epoch_top5=0, time=0.0)
         if a.resume and os.path.exists(a.resume):
@@ -478,6 +503,28 @@ class Trainer:
             self.ddp.sync_buffers()
             if self.comm.world_size > 1:
                 self.comm.broadcast_(self.arena.P, 0)
+        # --model-ema: the average starts as a copy of the weights every rank now holds (after the rank-0 broadcast
+        # and a --resume load), or continues from the checkpoint's
+        self.ema = None
+        if getattr(a, "model_ema", 0.0) > 0.0:
+            from .ema import ModelEma
+            native = self.kernels != "torch" and self.device.type == "cuda"
+            self.ema = ModelEma(arena, model, a.model_ema, warmup=getattr(a, "model_ema_warmup", False),
+                                native=native, refresh=self.native.refresh_shadows if self.native else None)
+            self.opt.ema = self.ema
+            self.best.setdefault("ema_top1", 0.0)
+            self.best.setdefault("ema_epoch_top1", 0)
+            _master_print(self.is_master, "Model EMA: decay {:g}{}; validated and saved beside the raw weights"
+                          .format(a.model_ema, " after the warm-up ramp (1 + t) / (10 + t)"
+                                  if self.ema.warmup else ""))
+            if self.start_epoch > 0:
+                saved = st.get("extra", {}).get("ema")
+                if saved is not None:
+                    self.ema.load_state_dict(saved)
+                    _master_print(self.is_master, f"Model EMA: resumed the average after {self.ema.updates} updates")
+                else:
+                    _master_print(self.is_master, f"Model EMA: {a.resume} holds no average; it starts from the "
+                                                  "loaded weights")
         ipe = self.train_sampler.num_batches(a.batch_size)
         gb = a.batch_size * self.ctx.world_size
         self.sched = Schedule(a.lr, a.epochs, ipe, a.lr_schedule, a.lr_step, a.lr_gamma, a.warmup_epochs,
@@ -530,12 +577,9 @@ class Trainer:
             else:
                 self.step.train_step(micro)
             if a.check_consistency and (it + 1) % a.check_consistency == 0:
-                self.ddp.check_consistency()
+                self.ddp.check_consistency(extra=self.ema.flats() if self.ema is not None else ())
             # one-time bucket rebuild from the observed ready order (iteration 1)
-            if getattr(self.ddp, "pending_relayout", None) is not None:
-                self.opt.set_flats(self.ddp.apply_pending_relayout(self.opt.flats()))
-                if self.native:
-                    self.native.rebind()
+            apply_relayout(self.ddp, self.opt, self.ema, self.native)
             micro = []
             it += 1
             nlog += 1
@@ -598,12 +642,25 @@ class Trainer:
             lr = self.last_lr
             va_loss, va1, va5, t_val = self.validate(val_loader)
             total += t_train + t_val
+            if self.ema is not None:
+                # the average in place of the weights (and of the BatchNorm statistics: validate()'s buffer broadcast
+                # then sends rank 0's averages), through the same eval forward; swapped back below, bit for bit
+                self.ema.swap()
+                ea_loss, ea1, ea5, t_ema = self.validate(val_loader)
+                total += t_ema
             # checkpoint I/O is not a hang: every rank disarms its watchdog BEFORE the master starts
             # writing (the others would otherwise start the next epoch, block in its first collective
             # and time out while the master writes), and all ranks meet in a barrier after the writes,
             # still disarmed; the next step's beat re-arms
             if self.watchdog:
                 self.watchdog.pause()
+            if self.ema is not None:
+                if ea1 > self.best["ema_top1"]:
+                    self.best["ema_top1"], self.best["ema_epoch_top1"] = ea1, epoch
+                    if self.is_master and a.save_model:  # written while the average is swapped in
+                        ckpt.save_best(self.model, a.arch, a.checkpoint_dir or ".",
+                                       name=f"imagenet_FR_{a.arch}_ema.pt")
+                self.ema.swap()
             if va1 > self.best["top1"]:   # imagenet.py:388-392
                 self.best["top1"], self.best["epoch_top1"] = va1, epoch
                 if self.is_master and a.save_model:
@@ -618,6 +675,9 @@ class Trainer:
                 print(f"\tTrain loss: {tr_loss} ; Test loss: {va_loss}")
                 print(f"\tTrain top1 accuracy: {tr1} ; Test top1 accuracy: {va1}")
                 print(f"\tTrain top5 accuracy: {tr5} ; Test top5 accuracy: {va5}")
+                if self.ema is not None:
+                    print(f"\tEMA Test loss: {ea_loss} ; EMA Test top1 accuracy: {ea1} ; "
+                          f"EMA Test top5 accuracy: {ea5}")
                 print(f"\tTrain time: {t_train} seconds; Test time:{t_val} seconds")
                 print(f"\tThroughput: {ips:.1f} img/s (job), {ips / self.ctx.world_size:.1f} img/s/GPU",
                       flush=True)
@@ -632,15 +692,22 @@ class Trainer:
                     self.tb.add_scalars("Loss", {"train": tr_loss, "val": va_loss}, epoch + 1)
                     self.tb.add_scalars("Top1 accuracy", {"train": tr1, "val": va1}, epoch + 1)
                     self.tb.add_scalars("Top5 accuracy", {"train": tr5, "val": va5}, epoch + 1)
+                    if self.ema is not None:  # one more series under the same tags
+                        self.tb.add_scalars("Loss", {"val_ema": ea_loss}, epoch + 1)
+                        self.tb.add_scalars("Top1 accuracy", {"val_ema": ea1}, epoch + 1)
+                        self.tb.add_scalars("Top5 accuracy", {"val_ema": ea5}, epoch + 1)
                     self.tb.add_scalar("lr", lr, epoch)
                     self.tb.add_scalar("throughput_img_s", ips, epoch + 1)
             history.append(dict(epoch=epoch + 1, lr=lr, train_loss=tr_loss, val_loss=va_loss, train_top1=tr1,
                                 val_top1=va1, train_top5=tr5, val_top5=va5, train_time=t_train,
                                 val_time=t_val, img_s=ips))
+            if self.ema is not None:
+                history[-1].update(val_ema_loss=ea_loss, val_ema_top1=ea1, val_ema_top5=ea5, val_ema_time=t_ema)
             if a.checkpoint_dir and self.is_master:
                 slow_save()  # fault injection (IMAGENT_FAULT_SLOW_SAVE)
                 ckpt.save_state(os.path.join(a.checkpoint_dir, f"state_{a.arch}.pt"), self.model, self.opt,
-                                epoch, self.best)
+                                epoch, self.best,
+                                extra={"ema": self.ema.state_dict()} if self.ema is not None else None)
             if self.watchdog and (a.save_model or a.checkpoint_dir):
                 self.ctx.barrier()  # nobody re-arms until the master's writes are done
             if not self.comm.healthy():
@@ -652,6 +719,9 @@ class Trainer:
             print(f"\t Best Test top1 accuracy: {self.best['top1']}")
             print(f"\tTop5 best epoch: {self.best['epoch_top5']}")
             print(f"\t Best Test top5 accuracy: {self.best['top5']}")
+            if self.ema is not None:
+                print(f"\tEMA top1 best epoch: {self.best['ema_epoch_top1']}")
+                print(f"\t Best EMA Test top1 accuracy: {self.best['ema_top1']}")
             print(f"\tTraining time: {total/60} minutes", flush=True)
         return dict(best=self.best, history=history)
 

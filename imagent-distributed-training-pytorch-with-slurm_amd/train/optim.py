@@ -16,6 +16,8 @@ reference, quirk Q5).
   same psi in mu_t = beta1 * (1 - 0.5 * 0.96 ** (t * psi))).
 * :class:`FlatLARS` - LARS for the large-batch (8192) configuration.
 * ``fr`` is deliberately absent: the reference never defines it.
+* every optimizer has an optional ``ema`` attribute (:class:`~imagent_amd.train.ema.ModelEma`, ``--model-ema``)
+  and updates it once after its own step.
 """
 
 from __future__ import annotations
@@ -41,6 +43,7 @@ class FlatSGD:
         self.buf: Optional[torch.Tensor] = None
         self.steps = 0
         self.grad_scale = 1.0
+        self.ema = None  # train/ema.py ModelEma: updated once per step()
 
     @property
     def lr(self) -> float:
@@ -80,6 +83,8 @@ class FlatSGD:
             ar.P.add_(d, alpha=-lr)
             if ar.S is not None:
                 ar.S.copy_(ar.P)
+        if self.ema is not None:
+            self.ema.update()
         self.steps += 1
         if self.after_step is not None:
             self.after_step()
@@ -176,6 +181,8 @@ class FlatLARS(FlatSGD):
                 w.sub_(v)
             if ar.S is not None:
                 ar.S.copy_(ar.P)
+        if self.ema is not None:
+            self.ema.update()
         self.steps += 1
         if self.after_step is not None:
             self.after_step()
@@ -195,6 +202,7 @@ class TorchOptimizer:
         self.after_step = after_step
         self.full_refresh = full_refresh
         self.steps = 0
+        self.ema = None  # train/ema.py ModelEma
 
     @property
     def param_groups(self):
@@ -214,6 +222,8 @@ class TorchOptimizer:
         self.steps += 1
         if self.full_refresh is not None:
             self.full_refresh()
+        if self.ema is not None:
+            self.ema.update()
 
     def state_dict(self):
         return {"kind": "torch", "state": self.opt.state_dict(), "steps": self.steps}
