@@ -93,8 +93,20 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--mixup and --cutmix together: the probability that a mixed sample is CutMix")
     # --- optimisation ---
     p.add_argument("--optimizer", default="sgd",
-                   choices=["sgd", "lars", "adam", "adamw", "adagrad", "rmsprop", "adadelta", "asgd", "nadam"])
+                   choices=["sgd", "lars", "lamb", "adam", "adamw", "adagrad", "rmsprop", "adadelta", "asgd", "nadam"],
+                   help="sgd, lars, lamb, adam and adamw are fused HIP launches over the flat parameter arena "
+                        "(profiles/flat_adam_lamb.md); the others are the stock torch.optim classes. adam, adamw and "
+                        "lamb do not combine with --hip-graph (their bias corrections are new kernel arguments on "
+                        "every step)")
     p.add_argument("--lars-eta", type=float, default=1e-3, help="LARS trust coefficient")
+    p.add_argument("--betas", type=float, nargs=2, default=[0.9, 0.999], metavar=("B1", "B2"),
+                   help="adam / adamw / lamb: the decay of the first and second moment")
+    p.add_argument("--opt-eps", type=float, default=None, metavar="EPS",
+                   help="adam / adamw / lamb: the denominator's epsilon (default 1e-8 for adam and adamw, 1e-6 for "
+                        "lamb)")
+    p.add_argument("--lamb-max-grad-norm", type=float, default=1.0, metavar="NORM",
+                   help="lamb: clip the gradient to this global L2 norm before the moments (one more launch over "
+                        "the gradient arena). 0: off")
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--wd", "--weight-decay", dest="wd", type=float, default=1e-4)
     p.add_argument("--nesterov", action="store_true")

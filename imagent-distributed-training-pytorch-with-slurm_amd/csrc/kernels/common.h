@@ -127,6 +127,13 @@ inline int device_cus() {
     return n;
 }
 
+// grid of a streaming (grid-stride) kernel: one block per `per_block` work items, capped at STREAM_GRID_CAP blocks
+constexpr int STREAM_GRID_CAP = 8192;
+inline int stream_grid(long work, int per_block = 256) {
+    long b = (work + per_block - 1) / per_block;
+    return (int)(b < STREAM_GRID_CAP ? (b > 0 ? b : 1) : STREAM_GRID_CAP);
+}
+
 #define IMK_CHECK_LAUNCH()                         \
     do {                                           \
         hipError_t e_ = hipGetLastError();         \

@@ -1286,11 +1286,6 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const TDesc* __r
     }
 }
 
-int stream_grid(long work, int per_block = 256) {
-    long b = (work + per_block - 1) / per_block;
-    return (int)(b < 8192 ? (b > 0 ? b : 1) : 8192);
-}
-
 }  // namespace
 
 IMK_EXPORT int imk_maxpool_fwd(const void* x, void* y, void* idx, int N, int H, int W, int C, int OH,

@@ -104,6 +104,12 @@ class LarsDesc(C.Structure):
                 ("n", C.c_long), ("adapt", C.c_int), ("pad", C.c_int)]
 
 
+class LambDesc(C.Structure):
+    """optim.hip LambDesc: one parameter tensor of the flat arena with its two Adam moments."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("shadow", C.c_void_p),
+                ("n", C.c_long), ("adapt", C.c_int), ("pad", C.c_int)]
+
+
 class EmaBufDesc(C.Structure):
     """optim.hip EmaBufDesc: one model buffer and where its average lies in the flat side buffer (train/ema.py)."""
     _fields_ = [("buf", C.c_void_p), ("off", C.c_long), ("n", C.c_long)]
@@ -231,6 +237,9 @@ def _declare(name: str, lib) -> None:
             "imk_quant_fp8_weights": [vp, i32, i64, i32, vp],
             "imk_qdesc_size": [], "imk_lars_desc_size": [],
             "imk_lars_step": [vp, i32, i64, vp, f32, f32, f32, f32, f32, i32, vp],
+            "imk_adam_flat": [vp, vp, vp, vp, vp, i64] + [f32] * 8 + [i32, f32, vp],
+            "imk_lamb_step": [vp, i32, vp, i32, vp, i64, vp] + [f32] * 10 + [vp],
+            "imk_lamb_desc_size": [], "imk_optim_const": [i32],
         }
         for fn, args in sigs.items():
             f = getattr(lib, fn)
@@ -242,7 +251,7 @@ def _declare(name: str, lib) -> None:
         for fn, st in [("imk_igemm_args_size", IGemmArgs), ("imk_wgrad_args_size", WgradArgs),
                        ("imk_bn_rundesc_size", RunDesc), ("imk_bn_affdesc_size", AffDesc), ("imk_tdesc_size", TDesc),
                        ("imk_qdesc_size", QDesc), ("imk_lars_desc_size", LarsDesc),
-                       ("imk_ema_bufdesc_size", EmaBufDesc)]:
+                       ("imk_ema_bufdesc_size", EmaBufDesc), ("imk_lamb_desc_size", LambDesc)]:
             n = getattr(lib, fn)()
             if n != C.sizeof(st):
                 raise RuntimeError(f"{fn}: native {n} B != ctypes {C.sizeof(st)} B - rebuild")

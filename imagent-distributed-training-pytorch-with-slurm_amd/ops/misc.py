@@ -281,6 +281,75 @@ def sgd_flat(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor],
                                       _lib.stream_ptr()), "sgd")
 
 
+def adam_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, shadow: Optional[torch.Tensor],
+              step_size: float, rbc2: float, eps: float, beta2: float, omb1: float, omb2: float, weight_decay: float,
+              lr_wd: float, decoupled: bool, grad_scale: float = 1.0) -> None:
+    """One Adam / AdamW step over the flat arenas (csrc/kernels/optim.hip adam_kernel): ``step_size = lr / (1 -
+    beta1^t)``, ``rbc2 = 1 / sqrt(1 - beta2^t)``, ``omb = 1 - beta``, ``lr_wd = 1 - lr * weight_decay`` (read by the
+    decoupled form only). ``g`` is read only; ``shadow`` (bf16, may be None) becomes ``bf16(p)``."""
+    n = p.numel()
+    for t in (p, g, m, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.data_ptr() % 16 == 0
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == n and shadow.is_contiguous()
+                              and shadow.data_ptr() % 8 == 0)
+    _lib.check(_lib.kernels().imk_adam_flat(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _lib.ptr(shadow),
+                                            n, step_size, rbc2, eps, beta2, omb1, omb2, weight_decay, lr_wd,
+                                            1 if decoupled else 0, grad_scale, _lib.stream_ptr()), "adam")
+
+
+def lamb_chunk() -> int:
+    """Elements per chunk (= per block) of the LAMB kernels."""
+    return _lib.kernels().imk_optim_const(0)
+
+
+class LambTable:
+    """The device tables of :func:`lamb_step` over a :class:`~imagent_amd.models.arena.ParamArena` (see
+    :func:`lamb_table`). ``norms`` after a step: ``sum w^2`` [T], ``sum r^2`` [T], ``sum g^2`` (0 with clipping
+    off)."""
+
+    def __init__(self, descs, chunks, norms, count, nchunks, g_flat):
+        self.descs, self.chunks, self.norms = descs, chunks, norms
+        self.count, self.nchunks, self.g_flat = count, nchunks, g_flat
+
+
+def lamb_table(arena, m: torch.Tensor, v: torch.Tensor) -> LambTable:
+    """Descriptor ``i`` is parameter ``i`` of ``arena`` with its slices of ``m`` and ``v`` (flat, ``arena.P``'s
+    offsets); ``adapt`` = more than one dimension. Beside it the chunk table: ``(tensor, first element)`` per
+    :func:`lamb_chunk` elements, tensor after tensor, a chunk never spanning two tensors."""
+    P, G, S = arena.P, arena.G, arena.S
+    T, chunk = len(arena.params), lamb_chunk()
+    for t in (P, G, m, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == arena.total
+        assert t.data_ptr() % 16 == 0
+    assert S is None or (S.numel() == arena.total and S.data_ptr() % 8 == 0)
+    d = (_lib.LambDesc * T)()
+    rows = []
+    for i in range(T):
+        o, n = arena.offsets[i], arena.numels[i]
+        assert o % 4 == 0 and 0 <= o and o + n <= arena.total  # f32x4 body from the first element of every slice
+        d[i].p, d[i].g = P[o:o + n].data_ptr(), G[o:o + n].data_ptr()
+        d[i].m, d[i].v = m[o:o + n].data_ptr(), v[o:o + n].data_ptr()
+        d[i].shadow = S[o:o + n].data_ptr() if S is not None else None
+        d[i].n = n
+        d[i].adapt = 1 if len(arena.shapes[i]) > 1 else 0
+        rows += [(i, f) for f in range(0, n, chunk)]
+    dev = P.device
+    descs = torch.frombuffer(bytearray(bytes(memoryview(d))), dtype=torch.uint8).to(dev)
+    chunks = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(dev)
+    norms = torch.zeros(2 * T + 1, dtype=torch.float32, device=dev)
+    return LambTable(descs, chunks, norms, T, len(rows), G)
+
+
+def lamb_step(tab: LambTable, lr: float, beta2: float, omb1: float, omb2: float, c1: float, c2: float, eps: float,
+              weight_decay: float, max_grad_norm: float, grad_scale: float = 1.0) -> None:
+    """One LAMB step over ``tab`` (csrc/kernels/optim.hip): a memset of the norms and two launches, three with
+    ``max_grad_norm > 0`` (the global gradient norm). ``c1 = 1 / (1 - beta1^t)``, ``c2 = 1 / sqrt(1 - beta2^t)``."""
+    _lib.check(_lib.kernels().imk_lamb_step(tab.descs.data_ptr(), tab.count, tab.chunks.data_ptr(), tab.nchunks,
+                                            tab.g_flat.data_ptr(), tab.g_flat.numel(), tab.norms.data_ptr(), lr,
+                                            beta2, omb1, omb2, c1, c2, eps, weight_decay, max_grad_norm, grad_scale,
+                                            _lib.stream_ptr()), "lamb step")
+
+
 def ema_flat(e: torch.Tensor, p: torch.Tensor, omd: float) -> None:
     """``e += omd * (p - e)`` over two flat fp32 arenas of one length."""
     assert e.numel() == p.numel() and e.dtype == p.dtype == torch.float32

@@ -251,6 +251,7 @@ class Trainer:
             raise SystemExit("--fp8-wgrad needs --dtype fp8 --kernels hip (the fp8 weight gradient reads the 1-byte "
                              f"copies of the fp8 forward and dgrad): got --dtype {a.dtype} --kernels {a.kernels}")
         self._check_augmentation(a)
+        self._check_optimizer(a)
         torch.manual_seed(a.seed)  # imagenet.py:215
         self.topo = launcher.discover(a.launcher)
         if not a.quiet_banner:
@@ -311,6 +312,24 @@ class Trainer:
         if ema_warm and getattr(a, "hip_graph", False):
             raise SystemExit("--model-ema-warmup with --hip-graph: the decay would be a new kernel argument on every "
                              "step, and every step a re-capture (a constant --model-ema is captured)")
+
+    @staticmethod
+    def _check_optimizer(a):
+        """--optimizer adam / adamw / lamb and their flags: refused here, before any model is built."""
+        name = getattr(a, "optimizer", "sgd")
+        if name not in ("adam", "adamw", "lamb"):
+            return
+        if getattr(a, "hip_graph", False):
+            raise SystemExit(f"--optimizer {name} with --hip-graph: the bias corrections 1 - beta^t are new kernel "
+                             "arguments on every step, and every step a re-capture (sgd and lars are captured)")
+        b1, b2 = getattr(a, "betas", (0.9, 0.999))
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise SystemExit(f"--betas {b1} {b2}: need 0 <= B < 1")
+        eps = getattr(a, "opt_eps", None)
+        if eps is not None and not eps > 0.0:
+            raise SystemExit(f"--opt-eps {eps}: need EPS > 0")
+        if not getattr(a, "lamb_max_grad_norm", 1.0) >= 0.0:
+            raise SystemExit(f"--lamb-max-grad-norm {a.lamb_max_grad_norm}: need NORM >= 0 (0: off)")
 
     def _build_data(self):
         a = self.args
@@ -469,7 +488,19 @@ class Trainer:
         full = (lambda: self.native.refresh_shadows(full=True)) if self.native else None
         self.opt = build_optimizer(a.optimizer, arena, a.lr, a.momentum, a.wd, a.nesterov,
                                    after_step=after, full_refresh=full,
-                                   schedule_decay=a.schedule_decay, lars_eta=a.lars_eta)
+                                   schedule_decay=a.schedule_decay, lars_eta=a.lars_eta,
+                                   betas=getattr(a, "betas", None), opt_eps=getattr(a, "opt_eps", None),
+                                   lamb_max_grad_norm=getattr(a, "lamb_max_grad_norm", 1.0))
+        if a.optimizer in ("adam", "adamw", "lamb"):
+            g = self.opt.param_groups[0]  # (native follows the arena's device, as FlatSGD and FlatLARS)
+            if a.optimizer == "lamb":
+                how = (f"a memset and {self.opt.launches()} HIP launches per step over {len(arena.params)} tensors in "
+                       f"fixed-size chunks, max grad norm {g['max_grad_norm']:g}") if self.opt.native else \
+                    "per-tensor torch ops"
+            else:
+                how = "one fused HIP launch per step over the flat arena" if self.opt.native else "flat torch ops"
+            _master_print(self.is_master, f"Optimizer: {a.optimizer} (betas {g['betas'][0]:g} {g['betas'][1]:g}, "
+                                          f"eps {g['eps']:g}): {how}")
         self.metrics = DeviceMetrics(self.device)
         from ..utils.profiling import StepTimer
         self.timer = StepTimer(enabled=self.device.type == "cuda")
