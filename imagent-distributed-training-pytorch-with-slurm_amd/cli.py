@@ -91,6 +91,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--mixup / --cutmix: the probability that a sample is mixed at all")
     p.add_argument("--mix-switch-prob", type=float, default=0.5, metavar="P",
                    help="--mixup and --cutmix together: the probability that a mixed sample is CutMix")
+    p.add_argument("--randaugment", type=int, default=None, metavar="M",
+                   help="RandAugment train augmentation at magnitude M (0 .. 30, 31 bins as torchvision's): every "
+                        "image goes through --randaug-ops ops drawn uniformly from the 14 of data/randaug.py, with a "
+                        "random sign, in integer arithmetic on the uint8 batch as stored -- ahead of the crop, so the "
+                        "fused crop + resize + normalise kernel is untouched (two HIP launches per op; validation "
+                        "never augments). Absent: off. Not with --hip-graph. Cost: profiles/randaug.md")
+    p.add_argument("--randaug-ops", type=int, default=2, metavar="N", help="--randaugment: ops per image (1 .. 4)")
+    p.add_argument("--randaug-fill", type=int, default=128, metavar="V",
+                   help="--randaugment: the colour (0 .. 255) of pixels a shear, translation or rotation brings in "
+                        "from outside the image; 128 is the normalised zero at mean = std = 0.5")
     # --- optimisation ---
     p.add_argument("--optimizer", default="sgd",
                    choices=["sgd", "lars", "lamb", "adam", "adamw", "adagrad", "rmsprop", "adadelta", "asgd", "nadam"],

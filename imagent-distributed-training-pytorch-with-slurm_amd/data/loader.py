@@ -15,6 +15,8 @@ CPU ``ToTensor/Normalize`` (``imagenet.py:119-120, 280-283, 346-359``):
   stem and optional random crop / horizontal flip are one HIP kernel; so is
   RandomResizedCrop (``rrc=``: boxes drawn on the device by ``data/augment.py``,
   crop + antialiased resize + normalise + flip fused, ``ops.misc.rrc_normalize_u8``);
+* RandAugment (``randaug=``, ``data/randaug.py``) is a uint8 -> uint8 stage of HIP kernels in front of those, on
+  the batch as stored;
 * workers are persistent (the reference re-forks 10 workers every epoch).
 """
 
@@ -36,7 +38,7 @@ class InputTransform:
 
     def __init__(self, backend: str, size: Tuple[int, int], mean=MEAN, std=STD, cpad: int = 8,
                  flip: bool = False, dtype=torch.float32, resize: bool = False, rrc=None,
-                 center_frac: Optional[float] = None, seed: int = 0, rank: int = 0):
+                 center_frac: Optional[float] = None, seed: int = 0, rank: int = 0, randaug=None):
         self.backend, self.size = backend, tuple(size)
         self.mean, self.std, self.cpad = tuple(mean), tuple(std), cpad
         self.flip = flip
@@ -60,6 +62,9 @@ class InputTransform:
         self.seed, self.rank, self.epoch = int(seed), int(rank), 0
         self._gen = None
         self._center = {}
+        # randaug: a data.randaug.RandAugment stage the uint8 batch passes through first, as stored and ahead of any
+        # crop (the train transform only); None: every path below is as it was
+        self.randaug = randaug
 
     def _epoch_seed(self) -> int:
         return (self.seed * 0x9E3779B1 + self.rank * 0x85EBCA6B + self.epoch * 0xC2B2AE35 + 1) % (2 ** 63 - 1)
@@ -115,9 +120,14 @@ class InputTransform:
         return out.to(self.dtype).contiguous()
 
     def __call__(self, u8: torch.Tensor, boxes: Optional[torch.Tensor] = None,
-                 flip: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 flip: Optional[torch.Tensor] = None, ra_params: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``boxes`` (int32 [B, 4] = top, left, h, w) / ``flip`` (uint8 [B]): explicit draws for the box path
-        instead of the transform's own (comparing backends on identical draws)."""
+        instead of the transform's own (comparing backends on identical draws); ``ra_params`` (int32 [B, L, 8])
+        likewise for the RandAugment stage."""
+        if self.randaug is not None:
+            u8 = self.randaug(u8, ra_params)
+        elif ra_params is not None:
+            raise ValueError("explicit ra_params need randaug=")
         if self.rrc is not None or self.center_frac is not None:
             return self._boxed(u8, boxes, flip)
         if boxes is not None or flip is not None:

@@ -505,6 +505,38 @@ def mix_pairs(x: torch.Tensor, pair: torch.Tensor, lam: torch.Tensor, boxes: tor
     return out
 
 
+def randaug_u8(images: torch.Tensor, params: torch.Tensor, fill: int = 128) -> torch.Tensor:
+    """RandAugment of a uint8 NHWC batch [B, H, W, 3] (csrc/kernels/randaug.hip): ``params`` int32 [B, L, 8], rows
+    ``(op, a0 .. a6)`` as ``data/randaug.py`` draws them, its L layers applied in order -- per layer one statistics
+    launch (the histograms of the images whose op needs the whole image) and one apply launch, from one buffer into
+    the other. Bit for bit ``data.randaug.randaug_torch``. ``images`` is never written; the result is a new tensor.
+    The stage is blind to the model's dtype, so the ``hip`` and ``hip_f32`` backends share it. The histogram scratch
+    and the two buffers come from the caching allocator and go back to it; nothing here synchronises with the
+    host."""
+    if images.dim() != 4 or images.shape[3] != 3 or images.dtype != torch.uint8 or not images.is_contiguous():
+        raise ValueError(f"randaug_u8: images {tuple(images.shape)} {images.dtype} (contiguous uint8 [B, H, W, 3])")
+    B, H, W, _ = images.shape
+    if params.dim() != 3 or params.shape[0] != B or params.shape[1] < 1 or params.shape[2] != 8:
+        raise ValueError(f"randaug_u8: params {tuple(params.shape)}, expected ({B}, L, 8)")
+    if not (0 <= int(fill) <= 255):
+        raise ValueError(f"randaug_u8: fill {fill} (0 .. 255)")
+    params = params.to(device=images.device, dtype=torch.int32).contiguous()
+    L = params.shape[1]
+    src, dst = images, torch.empty_like(images)
+    if B == 0 or H == 0 or W == 0:
+        return dst
+    hist = torch.empty((B, 4, 256), dtype=torch.int32, device=images.device)
+    k, st = _lib.kernels(), _lib.stream_ptr()
+    for layer in range(L):
+        _lib.check(k.imk_randaug_stats(src.data_ptr(), params.data_ptr(), hist.data_ptr(), B, H, W, L, layer, st),
+                   "randaugment statistics")
+        _lib.check(k.imk_randaug_apply(src.data_ptr(), dst.data_ptr(), params.data_ptr(), hist.data_ptr(), B, H, W,
+                                       L, layer, int(fill), st), "randaugment apply")
+        if layer + 1 < L:  # the next layer reads what this one wrote, into the other buffer (never into `images`)
+            src, dst = dst, (src if src is not images else torch.empty_like(images))
+    return dst
+
+
 def normalize_u8(images: torch.Tensor, out_hw, cpad: int, mean: Sequence[float], std: Sequence[float],
                  crop: Optional[torch.Tensor] = None, flip: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -304,6 +304,19 @@ class Trainer:
         if (mu > 0.0 or cm > 0.0) and getattr(a, "hip_graph", False):
             raise SystemExit("--mixup / --cutmix with --hip-graph: the per-batch draws are not fed into a captured "
                              "step")
+        ra = getattr(a, "randaugment", None)
+        if ra is not None:
+            from ..data.randaug import check_randaug
+            try:
+                check_randaug(getattr(a, "randaug_ops", 2), ra)
+            except ValueError as e:
+                raise SystemExit(f"--randaugment / --randaug-ops: {e}")
+            rf = getattr(a, "randaug_fill", 128)
+            if not (0 <= rf <= 255):
+                raise SystemExit(f"--randaug-fill {rf}: need 0 <= V <= 255")
+            if getattr(a, "hip_graph", False):
+                raise SystemExit("--randaugment with --hip-graph: the per-batch draws are not fed into a captured "
+                                 "step")
         ema, ema_warm = getattr(a, "model_ema", 0.0), getattr(a, "model_ema_warmup", False)
         if ema != 0.0 and not (0.0 < ema < 1.0):
             raise SystemExit(f"--model-ema {ema}: need 0 < DECAY < 1 (0: off)")
@@ -399,9 +412,19 @@ class Trainer:
         # the validation centre box goes through the antialiased path whenever the train boxes do (or a fraction is
         # asked for); with neither flag the transforms are the existing ones, byte for byte
         center = vc if (rrc is not None or vc != 1.0) else None
+        # RandAugment of the uint8 batch as stored, ahead of the train transform's crop (data/randaug.py);
+        # validation never augments
+        self.randaug = None
+        if getattr(a, "randaugment", None) is not None:
+            from ..data.randaug import RandAugment
+            self.randaug = RandAugment(self.kernels, getattr(a, "randaug_ops", 2), a.randaugment,
+                                       getattr(a, "randaug_fill", 128), seed=a.seed, rank=rk)
+            _master_print(self.is_master, "Augmentation: RandAugment {} ops at magnitude {} of 30, fill {}, on the "
+                          "stored uint8 images ahead of the crop".format(self.randaug.num_ops, self.randaug.magnitude,
+                                                                         self.randaug.fill))
         self.transform_train = InputTransform(self.kernels, size, cpad=resnet.ResNet.STEM_CPAD,
                                               flip=a.flip, dtype=torch.float32, resize=rs, rrc=rrc, seed=a.seed,
-                                              rank=rk)
+                                              rank=rk, randaug=self.randaug)
         self.transform_val = InputTransform(self.kernels, size, cpad=resnet.ResNet.STEM_CPAD,
                                             dtype=torch.float32, resize=rs, center_frac=center)
         if rrc is not None:
@@ -427,6 +450,8 @@ class Trainer:
         self.transform_train.set_epoch(epoch)  # the epoch's RandomResizedCrop boxes and flips (a resume repeats them)
         if self.mixer is not None:
             self.mixer.set_epoch(epoch)  # and its Mixup / CutMix draws
+        if self.randaug is not None:
+            self.randaug.set_epoch(epoch)  # and its RandAugment draws
         if a.data == "synthetic":
             nt = self.train_sampler.num_batches(a.batch_size)
             nv = self.val_sampler.num_batches(a.batch_size)
