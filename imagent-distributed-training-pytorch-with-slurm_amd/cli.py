@@ -101,6 +101,28 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--randaug-fill", type=int, default=128, metavar="V",
                    help="--randaugment: the colour (0 .. 255) of pixels a shear, translation or rotation brings in "
                         "from outside the image; 128 is the normalised zero at mean = std = 0.5")
+    p.add_argument("--trivialaugment", action="store_true",
+                   help="TrivialAugmentWide train augmentation (torchvision's ta_wide): every image goes through one "
+                        "op drawn uniformly from the same 14, at a magnitude bin drawn uniformly from 0 .. 30 over the "
+                        "wide ranges of data/trivialaug.py, through --randaugment's kernels and in its place (takes "
+                        "--randaug-fill; not with --randaugment, not with --hip-graph)")
+    p.add_argument("--random-erase", type=float, default=0.0, metavar="P",
+                   help="Random Erasing train augmentation: with probability P a sample's model input has "
+                        "--erase-count boxes overwritten in place by one HIP kernel, after the normalise / crop kernel "
+                        "and before Mixup / CutMix (torchvision's RandomErasing, timm's count and pixel mode; "
+                        "validation never erases). 0: off. Not with --hip-graph. Cost: profiles/erase.md")
+    p.add_argument("--erase-scale", type=float, nargs=2, default=[0.02, 0.33], metavar=("LO", "HI"),
+                   help="--random-erase: the erased share of the image area, 0 < LO <= HI <= 1")
+    p.add_argument("--erase-ratio", type=float, nargs=2, default=[0.3, 3.3], metavar=("LO", "HI"),
+                   help="--random-erase: the boxes' aspect ratio h / w, log-uniform, 0 < LO <= HI")
+    p.add_argument("--erase-count", type=int, default=1, metavar="N",
+                   help="--random-erase: boxes per erased sample (1 .. 4), each of the drawn area divided by N")
+    p.add_argument("--erase-mode", default="const", choices=["const", "pixel"],
+                   help="--random-erase: const -- every erased element becomes --erase-value; pixel -- an independent "
+                        "N(0, 1) draw per element, generated in the kernel (Philox4x32-10, Box-Muller)")
+    p.add_argument("--erase-value", type=float, default=0.0, metavar="V",
+                   help="--random-erase --erase-mode const: the value written, in normalised units (0: the mean "
+                        "colour)")
     # --- optimisation ---
     p.add_argument("--optimizer", default="sgd",
                    choices=["sgd", "lars", "lamb", "adam", "adamw", "adagrad", "rmsprop", "adadelta", "asgd", "nadam"],

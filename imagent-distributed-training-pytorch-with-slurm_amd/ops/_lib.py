@@ -228,6 +228,7 @@ def _declare(name: str, lib) -> None:
             "imk_resize_normalize_u8": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
             "imk_rrc_normalize_u8": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp],
             "imk_mix_pairs": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+            "imk_erase_boxes": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
             "imk_randaug_stats": [vp, vp, vp, i32, i32, i32, i32, i32, vp],
             "imk_randaug_apply": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
             "imk_transpose_batched": [vp, i32, i32, vp],

@@ -505,6 +505,37 @@ def mix_pairs(x: torch.Tensor, pair: torch.Tensor, lam: torch.Tensor, boxes: tor
     return out
 
 
+def erase_boxes(x: torch.Tensor, boxes: torch.Tensor, keys: Optional[torch.Tensor], mode: str = "const",
+                value: float = 0.0) -> torch.Tensor:
+    """Random Erasing of a batch **in place**, one HIP kernel (csrc/kernels/erase.hip erase_boxes_kernel): ``x`` NHWC
+    [B, H, W, Cp] (bf16 or fp32, Cp 4 or 8, as the normalise kernels leave it), ``boxes`` int32 [B, N, 4] = (top,
+    left, h, w), ``keys`` int32 [B, 2] (``pixel`` mode; may be None in ``const`` mode). Inside a box channels 0 .. 2
+    become ``value`` (``const``; taken as fp32, round-to-nearest-even to bf16) or the pixel's N(0, 1) noise
+    (``pixel``: Philox4x32-10 on (key, pixel) through Box-Muller, ``data/erase.py``), the pad channels zero; nothing
+    outside the boxes is touched, and the work follows the boxes' area. Returns ``x``. The draws come from
+    ``data/erase.py``; nothing here synchronises with the host."""
+    if x.dim() != 4 or not x.is_contiguous() or x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"erase_boxes: x {tuple(x.shape)} {x.dtype} (contiguous NHWC, bf16 or fp32)")
+    B, H, W, Cp = x.shape
+    if Cp not in (4, 8):
+        raise ValueError(f"erase_boxes: {Cp} channels (the padded 4 or 8 of the model input)")
+    if mode not in ("const", "pixel"):
+        raise ValueError(f"erase_boxes: mode {mode!r} (const or pixel)")
+    if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[1] < 1 or boxes.shape[2] != 4:
+        raise ValueError(f"erase_boxes: boxes {tuple(boxes.shape)}, expected ({B}, N, 4)")
+    if mode == "pixel" and (keys is None or tuple(keys.shape) != (B, 2)):
+        raise ValueError(f"erase_boxes: pixel mode needs keys of shape ({B}, 2)")
+    boxes = boxes.to(device=x.device, dtype=torch.int32).contiguous()
+    if keys is not None:
+        keys = keys.to(device=x.device, dtype=torch.int32).contiguous()
+    if x.numel() == 0:
+        return x
+    _lib.check(_lib.kernels().imk_erase_boxes(x.data_ptr(), boxes.data_ptr(), _lib.ptr(keys), B, boxes.shape[1], H, W,
+                                              Cp, 1 if x.dtype == torch.float32 else 0, 1 if mode == "pixel" else 0,
+                                              float(value), _lib.stream_ptr()), "erase boxes")
+    return x
+
+
 def randaug_u8(images: torch.Tensor, params: torch.Tensor, fill: int = 128) -> torch.Tensor:
     """RandAugment of a uint8 NHWC batch [B, H, W, 3] (csrc/kernels/randaug.hip): ``params`` int32 [B, L, 8], rows
     ``(op, a0 .. a6)`` as ``data/randaug.py`` draws them, its L layers applied in order -- per layer one statistics

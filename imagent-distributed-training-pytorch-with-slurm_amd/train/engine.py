@@ -317,6 +317,33 @@ class Trainer:
             if getattr(a, "hip_graph", False):
                 raise SystemExit("--randaugment with --hip-graph: the per-batch draws are not fed into a captured "
                                  "step")
+        if getattr(a, "trivialaugment", False):
+            if ra is not None:
+                raise SystemExit("--trivialaugment with --randaugment: one policy or the other")
+            rf = getattr(a, "randaug_fill", 128)
+            if not (0 <= rf <= 255):
+                raise SystemExit(f"--randaug-fill {rf}: need 0 <= V <= 255")
+            if getattr(a, "hip_graph", False):
+                raise SystemExit("--trivialaugment with --hip-graph: the per-batch draws are not fed into a captured "
+                                 "step")
+        re_p = getattr(a, "random_erase", 0.0)
+        if not (0.0 <= re_p <= 1.0):
+            raise SystemExit(f"--random-erase {re_p}: need 0 <= P <= 1 (0: off)")
+        es, er = getattr(a, "erase_scale", (0.02, 0.33)), getattr(a, "erase_ratio", (0.3, 3.3))
+        if not (0.0 < es[0] <= es[1] <= 1.0):
+            raise SystemExit(f"--erase-scale {es[0]} {es[1]}: need 0 < LO <= HI <= 1")
+        if not (0.0 < er[0] <= er[1]) or not math.isfinite(er[1]):
+            raise SystemExit(f"--erase-ratio {er[0]} {er[1]}: need 0 < LO <= HI")
+        ec = getattr(a, "erase_count", 1)
+        if not (1 <= ec <= 4):
+            raise SystemExit(f"--erase-count {ec}: need 1 <= N <= 4")
+        if getattr(a, "erase_mode", "const") not in ("const", "pixel"):
+            raise SystemExit(f"--erase-mode {a.erase_mode}: const or pixel")
+        if not math.isfinite(getattr(a, "erase_value", 0.0)):
+            raise SystemExit(f"--erase-value {a.erase_value}: need a finite number")
+        if re_p > 0.0 and getattr(a, "hip_graph", False):
+            raise SystemExit("--random-erase with --hip-graph: the per-batch draws are not fed into a captured "
+                             "step")
         ema, ema_warm = getattr(a, "model_ema", 0.0), getattr(a, "model_ema_warmup", False)
         if ema != 0.0 and not (0.0 < ema < 1.0):
             raise SystemExit(f"--model-ema {ema}: need 0 < DECAY < 1 (0: off)")
@@ -422,6 +449,11 @@ class Trainer:
             _master_print(self.is_master, "Augmentation: RandAugment {} ops at magnitude {} of 30, fill {}, on the "
                           "stored uint8 images ahead of the crop".format(self.randaug.num_ops, self.randaug.magnitude,
                                                                          self.randaug.fill))
+        elif getattr(a, "trivialaugment", False):  # the same stage, drawing data/trivialaug.py's rows
+            from ..data.trivialaug import TrivialAugmentWide
+            self.randaug = TrivialAugmentWide(self.kernels, getattr(a, "randaug_fill", 128), seed=a.seed, rank=rk)
+            _master_print(self.is_master, "Augmentation: TrivialAugmentWide, one op at a bin of 0 .. 30, fill {}, on "
+                          "the stored uint8 images ahead of the crop".format(self.randaug.fill))
         self.transform_train = InputTransform(self.kernels, size, cpad=resnet.ResNet.STEM_CPAD,
                                               flip=a.flip, dtype=torch.float32, resize=rs, rrc=rrc, seed=a.seed,
                                               rank=rk, randaug=self.randaug)
@@ -433,6 +465,18 @@ class Trainer:
         if center is not None:
             _master_print(self.is_master, "Validation: centre crop {:g} of each side -> {}x{}, antialiased"
                           .format(center, *size))
+        # Random Erasing of every training micro-batch's model input, in place and ahead of the mixer
+        # (data/erase.py); validation never erases
+        self.eraser = None
+        if getattr(a, "random_erase", 0.0) > 0.0:
+            from ..data.erase import BatchEraser
+            self.eraser = BatchEraser(self.kernels, a.random_erase, tuple(a.erase_scale), tuple(a.erase_ratio),
+                                      a.erase_count, a.erase_mode, a.erase_value, seed=a.seed, rank=rk)
+            fill = "N(0, 1) noise per element" if a.erase_mode == "pixel" else f"the value {a.erase_value:g}"
+            _master_print(self.is_master, "Augmentation: Random Erasing with probability {:g}, {} box{} of scale "
+                          "({:g}, {:g}) ratio ({:g}, {:g}), filled with {}".format(
+                              a.random_erase, a.erase_count, "" if a.erase_count == 1 else "es", *self.eraser.scale,
+                              *self.eraser.ratio, fill))
         # Mixup / CutMix of every training micro-batch with itself (data/mix.py); validation never mixes
         self.mixer = None
         mu, cm = getattr(a, "mixup", 0.0), getattr(a, "cutmix", 0.0)
@@ -451,7 +495,9 @@ class Trainer:
         if self.mixer is not None:
             self.mixer.set_epoch(epoch)  # and its Mixup / CutMix draws
         if self.randaug is not None:
-            self.randaug.set_epoch(epoch)  # and its RandAugment draws
+            self.randaug.set_epoch(epoch)  # and its RandAugment / TrivialAugmentWide draws
+        if self.eraser is not None:
+            self.eraser.set_epoch(epoch)  # and its Random Erasing draws
         if a.data == "synthetic":
             nt = self.train_sampler.num_batches(a.batch_size)
             nv = self.val_sampler.num_batches(a.batch_size)
@@ -617,6 +663,8 @@ class Trainer:
                 break
             data_wait += time.perf_counter() - tw
             data_time.update(time.perf_counter() - tw)
+            if self.eraser is not None:  # on the current stream, in place on the HIP paths
+                x = self.eraser(x)
             if self.mixer is not None:  # on the current stream: y becomes the (ya, yb, lam) triple
                 x, y = self.mixer(x, y)
             micro.append((x, y))
