@@ -82,6 +82,17 @@ def _run(cmd: List[str]) -> None:
 
 
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
+# per-file additions: the grouped convs are compiled without the packed fp32 VALU forms (v_pk_*_f32)
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"conv_group.hip": NO_PK_F32}
+
+
+def _file_flags(src: str) -> List[str]:
+    return FILE_FLAGS.get(os.path.basename(src), [])
+
+
+def _file_flags_key() -> List[str]:
+    return [f"{k}:{' '.join(v)}" for k, v in sorted(FILE_FLAGS.items())]
 
 
 def _compile_hip_object(src: str, obj: str, extra: List[str]) -> str:
@@ -94,14 +105,14 @@ def build_kernels(force: bool = False, jobs: int = 8) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
     hdrs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")))
     out = os.path.join(OUT, "libimagent_kernels.so")
-    key = ["kernels", ARCH] + HIP_FLAGS
+    key = ["kernels", ARCH] + HIP_FLAGS + _file_flags_key()
     if not force and not _stale(srcs + hdrs, out, key):
         return out
     objdir = os.path.join(OUT, "obj")
     os.makedirs(objdir, exist_ok=True)
     objs = [os.path.join(objdir, os.path.basename(s) + ".o") for s in srcs]
     with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        list(ex.map(lambda so: _compile_hip_object(so[0], so[1], []), zip(srcs, objs)))
+        list(ex.map(lambda so: _compile_hip_object(so[0], so[1], _file_flags(so[0])), zip(srcs, objs)))
     tl = _torch_lib_dir()
     _run([_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + objs +
          [f"-L{tl}", f"-Wl,-rpath,{tl}"])
@@ -116,13 +127,14 @@ def build_kernels_variant(tag: str, defines: List[str], jobs: int = 8) -> str:
     hdrs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")))
     d = os.path.join(OUT, "ab", tag)
     out = os.path.join(d, "libimagent_kernels.so")
-    key = ["kernels", ARCH] + HIP_FLAGS + list(defines)
+    key = ["kernels", ARCH] + HIP_FLAGS + _file_flags_key() + list(defines)
     if not _stale(srcs + hdrs, out, key):
         return out
     os.makedirs(os.path.join(d, "obj"), exist_ok=True)
     objs = [os.path.join(d, "obj", os.path.basename(x) + ".o") for x in srcs]
     with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
-        list(ex.map(lambda so: _compile_hip_object(so[0], so[1], list(defines)), zip(srcs, objs)))
+        list(ex.map(lambda so: _compile_hip_object(so[0], so[1], _file_flags(so[0]) + list(defines)),
+                    zip(srcs, objs)))
     tl = _torch_lib_dir()
     _run([_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + objs +
          [f"-L{tl}", f"-Wl,-rpath,{tl}"])

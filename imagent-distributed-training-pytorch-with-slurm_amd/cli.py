@@ -31,7 +31,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--save-model", action="store_true", default=False, help="save the best model")
     # --- model / data ---
     p.add_argument("--arch", default="resnet18", choices=["resnet18", "resnet34", "resnet50", "resnet101",
-                                                           "resnet152"])
+                                                           "resnet152", "resnext50_32x4d", "resnext101_32x8d",
+                                                           "resnext101_64x4d"],
+                   help="resnext*: grouped bottlenecks (conv2 on the grouped HIP kernels, bf16; --dtype fp8 keeps "
+                        "those convs bf16; not with --dtype fp32 on the HIP kernels)")
     p.add_argument("--image-size", type=int, default=448)
     p.add_argument("--deterministic", action="store_true",
                    help="BatchNorm statistics without float atomics (fixed-order reduction passes): two runs "

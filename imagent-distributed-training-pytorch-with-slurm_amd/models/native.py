@@ -23,7 +23,7 @@ import torch
 from ..ops import _lib
 from ..ops.block import BlockFn
 from ..ops.bn import BNActFn, bn_eval, running_update
-from ..ops.conv import ConvFn, LinearFn, conv_out_size, deterministic, igemm_fwd
+from ..ops.conv import ConvFn, LinearFn, conv_out_size, deterministic, gconv_fwd, igemm_fwd
 from ..ops.misc import AvgPoolFn, BNReluPoolFn, MaxPoolFn, StemFn, TransposePlan, maxpool_eval, stem_fused_ok
 from .arena import ParamArena
 from .resnet import BasicBlock, BatchNorm2d, BNWork, Bottleneck, Conv2d, Linear, ResNet
@@ -106,7 +106,8 @@ class NativeState:
         t_numel = 0
         convs: List[Conv2d] = m.convs()
         for c in convs:
-            sh = ar.shadow(c.weight).view(c.out_channels, c.kh, c.kw, c.in_channels)
+            # (a grouped conv: [C][3][3][cg], output channel x tap x input channel within the group)
+            sh = ar.shadow(c.weight).view(c.out_channels, c.kh, c.kw, c.in_channels // c.groups)
             c.w_bf16 = sh
             c.grad_pad = None
             if c is not m.conv1:
@@ -120,6 +121,18 @@ class NativeState:
             if c is m.conv1:
                 continue
             n = c.w_bf16.numel()
+            if c.groups > 1:
+                # the per-group transpose wt[g cg + ci][t][co in group] = w[g cg + co in group][t][ci]: each group's
+                # [cg][T][cg] block is contiguous in both shadows, one item of the batched launch per group
+                cg, blk = c.in_channels // c.groups, n // c.groups
+                if c.in_channels != c.out_channels:
+                    raise ValueError("grouped conv: equal input and output widths only")
+                c.wt_bf16 = self.T[off:off + n].view(c.in_channels, c.kh, c.kw, cg)
+                src, dst = c.w_bf16.view(-1), self.T[off:off + n]
+                for g in range(c.groups):
+                    st_items.append((src[g * blk:(g + 1) * blk], dst[g * blk:(g + 1) * blk], cg, c.kh * c.kw, cg))
+                off += n
+                continue
             c.wt_bf16 = self.T[off:off + n].view(c.in_channels, c.kh, c.kw, c.out_channels)
             st_items.append((c.w_bf16, c.wt_bf16, c.out_channels, c.kh * c.kw, c.in_channels))
             off += n
@@ -253,7 +266,7 @@ class Fp8State:
         convs = [c for c in m.convs() if c is not m.conv1]
         self.wq = WeightQuantizer([c.weight for c in convs], st.device, transposed=backward)
         for c, v, vt, i in zip(convs, self.wq.views, self.wq.views_t, range(len(convs))):
-            c.w8 = v.view(c.out_channels, c.kh, c.kw, c.in_channels)
+            c.w8 = v.view(c.out_channels, c.kh, c.kw, c.in_channels // c.groups)  # (grouped convs never read it)
             c.wt8 = vt  # [Ci][KH][KW][Co] e4m3 (fp8 dgrad) or None
             c.w8_exp = self.wq.exp[i:i + 1]
         bns = m.batchnorms()
@@ -334,6 +347,8 @@ def bind_native(model: ResNet, device, order: Optional[Sequence[int]] = None,
 def _conv(x, conv: Conv2d, bn: Optional[BatchNorm2d], train: bool):
     if train:
         return ConvFn.apply(x, conv.weight, conv, bn.work if bn is not None else None)
+    if conv.groups > 1:
+        return gconv_fwd(x, conv.w_bf16, conv.stride, conv.groups)
     return igemm_fwd(x, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw,
                      stem=getattr(conv, "stem", False))
 
@@ -441,6 +456,9 @@ def _forward_eval(model: ResNet, x: torch.Tensor) -> torch.Tensor:
 
     def conv(h, c, bn, relu, out=None, accumulate=False):
         aff = bn._eval_aff if st is not None else _affine(bn)
+        if c.groups > 1:  # (never a block's last conv: no shortcut to accumulate onto)
+            assert out is None and not accumulate
+            return gconv_fwd(h, c.w_bf16, c.stride, c.groups, affine=aff, relu=relu)
         return igemm_fwd(h, c.w_bf16, c.stride, c.padding, c.kh, c.kw, stem=getattr(c, "stem", False),
                          affine=aff, relu=relu, out=out, accumulate=accumulate)
 

@@ -1,4 +1,4 @@
-"""ResNet-18/34/50/101/152 with torchvision-identical parameter names.
+"""ResNet-18/34/50/101/152 and ResNeXt-50 32x4d / -101 32x8d / -101 64x4d with torchvision-identical parameter names.
 
 The reference instantiates ``torchvision.models.resnet18(pretrained=False,
 num_classes=1000)`` (``/root/reference/imagenet.py:312``); torchvision is not
@@ -37,12 +37,14 @@ import torch.nn.functional as F
 # --------------------------------------------------------------------------
 
 class Conv2d(nn.Module):
-    def __init__(self, cin: int, cout: int, k: int, stride: int = 1, padding: int = 0):
+    def __init__(self, cin: int, cout: int, k: int, stride: int = 1, padding: int = 0, groups: int = 1):
         super().__init__()
+        if cin % groups or cout % groups:
+            raise ValueError(f"Conv2d: {cin} -> {cout} channels do not split into {groups} groups")
         self.in_channels, self.out_channels = cin, cout
         self.kh = self.kw = k
-        self.stride, self.padding = stride, padding
-        w = torch.empty(cout, cin, k, k)
+        self.stride, self.padding, self.groups = stride, padding, groups
+        w = torch.empty(cout, cin // groups, k, k)
         nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu")
         self.weight = nn.Parameter(w.contiguous(memory_format=torch.channels_last))
         # bf16 shadows bound by ResNet.bind_native()
@@ -50,11 +52,12 @@ class Conv2d(nn.Module):
         self.wt_bf16: Optional[torch.Tensor] = None
 
     def forward_torch(self, x):
-        return F.conv2d(x, self.weight.to(x.dtype), None, self.stride, self.padding)
+        return F.conv2d(x, self.weight.to(x.dtype), None, self.stride, self.padding, 1, self.groups)
 
     def extra_repr(self):
         return (f"{self.in_channels}, {self.out_channels}, kernel_size=({self.kh}, {self.kw}), "
-                f"stride=({self.stride}, {self.stride}), padding=({self.padding}, {self.padding})")
+                f"stride=({self.stride}, {self.stride}), padding=({self.padding}, {self.padding})" +
+                (f", groups={self.groups}" if self.groups > 1 else ""))
 
 
 class BatchNorm2d(nn.Module):
@@ -114,8 +117,10 @@ class BNWork:
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64):
         super().__init__()
+        if groups != 1 or width_per_group != 64:
+            raise ValueError("BasicBlock only supports groups=1 and width_per_group=64")
         self.conv1 = Conv2d(inplanes, planes, 3, stride, 1)
         self.bn1 = BatchNorm2d(planes)
         self.conv2 = Conv2d(planes, planes, 3, 1, 1)
@@ -137,13 +142,14 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64):
         super().__init__()
-        self.conv1 = Conv2d(inplanes, planes, 1)
-        self.bn1 = BatchNorm2d(planes)
-        self.conv2 = Conv2d(planes, planes, 3, stride, 1)
-        self.bn2 = BatchNorm2d(planes)
-        self.conv3 = Conv2d(planes, planes * 4, 1)
+        width = int(planes * width_per_group / 64) * groups  # torchvision's rule (ResNeXt: groups > 1)
+        self.conv1 = Conv2d(inplanes, width, 1)
+        self.bn1 = BatchNorm2d(width)
+        self.conv2 = Conv2d(width, width, 3, stride, 1, groups=groups)
+        self.bn2 = BatchNorm2d(width)
+        self.conv3 = Conv2d(width, planes * 4, 1)
         self.bn3 = BatchNorm2d(planes * 4)
         self.downsample = downsample
         self.stride = stride
@@ -170,9 +176,11 @@ class ResNet(nn.Module):
     STEM_CPAD = 4
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: List[int],
-                 num_classes: int = 1000, zero_init_residual: bool = False):
+                 num_classes: int = 1000, zero_init_residual: bool = False, groups: int = 1,
+                 width_per_group: int = 64):
         super().__init__()
         self.block = block
+        self.groups, self.width_per_group = groups, width_per_group
         self.inplanes = 64
         self.conv1 = Conv2d(3, 64, 7, 2, 3)
         self.bn1 = BatchNorm2d(64)
@@ -195,10 +203,11 @@ class ResNet(nn.Module):
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride),
                                        BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        gw = dict(groups=self.groups, width_per_group=self.width_per_group)
+        layers = [block(self.inplanes, planes, stride, downsample, **gw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **gw))
         return nn.Sequential(*layers)
 
     def blocks(self):
@@ -256,8 +265,23 @@ def resnet152(**kw) -> ResNet:
     return _resnet(Bottleneck, [3, 8, 36, 3], **kw)
 
 
+def resnext50_32x4d(**kw) -> ResNet:
+    return _resnet(Bottleneck, [3, 4, 6, 3], groups=32, width_per_group=4, **kw)
+
+
+def resnext101_32x8d(**kw) -> ResNet:
+    return _resnet(Bottleneck, [3, 4, 23, 3], groups=32, width_per_group=8, **kw)
+
+
+def resnext101_64x4d(**kw) -> ResNet:
+    return _resnet(Bottleneck, [3, 4, 23, 3], groups=64, width_per_group=4, **kw)
+
+
 ARCHS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101,
-         "resnet152": resnet152}
+         "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d, "resnext101_32x8d": resnext101_32x8d,
+         "resnext101_64x4d": resnext101_64x4d}
+# the grouped-bottleneck archs: bf16 HIP kernels (ops/conv.py gconv_*) or the torch backend, no fp32 HIP path
+GROUPED_ARCHS = ("resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d")
 
 
 def build(arch: str, num_classes: int = 1000, **kw) -> ResNet:

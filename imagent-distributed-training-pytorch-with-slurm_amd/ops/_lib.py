@@ -162,6 +162,10 @@ def _declare(name: str, lib) -> None:
             "imk_conv_wgrad": [C.POINTER(WgradArgs), i32, vp],
             "imk_conv_wgrad_variant": [C.POINTER(WgradArgs), i32, i32, vp],
             "imk_conv_wgrad_fp8": [C.POINTER(WgradArgs), vp, vp, i32, i32, vp],
+            # grouped 3x3 convs (conv_group.hip)
+            "imk_gconv_fwd": [vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp],
+            "imk_gconv_dgrad": [vp, vp, vp] + [i32] * 8 + [vp],
+            "imk_gconv_wgrad": [vp, vp, vp] + [i32] * 8 + [vp],
             "imk_probe_ds_read_tr8": [vp, i32, vp, vp],
             "imk_conv_launches": [],
             # fp32 path (f32.hip)

@@ -35,7 +35,7 @@ from . import _lib, streams
 from . import conv as _conv
 from .bn import bn_act_backward, bn_act_forward, bn_apply_backward, bn_scale_shift
 from .bn_gram import GramBN, gram_T, gram_coef, gram_dgrad, gram_fwd_stats, gram_wgrad
-from .conv import BNBwdFuse, conv_wgrad, igemm_dgrad, igemm_fwd
+from .conv import BNBwdFuse, conv_wgrad, gconv_dgrad, gconv_fwd, igemm_dgrad, igemm_fwd
 
 
 # Each weight gradient is issued after the BN-backward pass that follows its dgrad, so the side stream's wgrad
@@ -155,6 +155,8 @@ def _xfuse_ok(conv, a, q) -> bool:
     """Can ``conv`` (the consumer of BN(a) + ReLU) apply that BN on its operand path?"""
     if not (_XFUSE and (q is None or not fp8_fwd_ok(conv)) and a.is_cuda) or _conv._NOSTREAM:
         return False
+    if _conv._grouped(conv):  # the grouped kernels stage the plain operand
+        return False
     if conv.kh == 1 and conv.kw == 1:
         return (conv.stride == 1 and conv.padding == 0 and conv.in_channels in (64, 128)
                 and conv.out_channels % 128 == 0)
@@ -167,6 +169,9 @@ def _xfuse_ok(conv, a, q) -> bool:
 
 
 def _fwd(conv, h, bn):
+    if _conv._grouped(conv):
+        _conv._gconv_mod_check(conv)
+        return gconv_fwd(h, conv.w_bf16, conv.stride, conv.groups, stats=bn.work)
     return igemm_fwd(h, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw,
                      stats=bn.work, stem=getattr(conv, "stem", False))
 
@@ -177,6 +182,8 @@ def _fwd(conv, h, bn):
 def fp8_fwd_ok(conv) -> bool:
     """Forward on fp8: 3x3 with >= 128 input channels, 1x1 with >= 512, or 256 into <= 128 channels (the
     1x1 convs with K <= 256 into wide outputs are HBM streams the bf16 streaming kernel runs faster)."""
+    if _conv._grouped(conv):  # grouped convs stay bf16
+        return False
     ci, co = conv.in_channels, conv.out_channels
     if conv.kh > 1:
         return ci >= 128
@@ -186,6 +193,8 @@ def fp8_fwd_ok(conv) -> bool:
 def fp8_dgrad_ok(conv) -> bool:
     """dgrad on fp8 (it gathers over the gradient's out_channels): 3x3 with >= 128, 1x1 with >= 512, or 256
     into <= 128 input channels (256 into wider: the bf16 streaming BN-backward dgrad wins)."""
+    if _conv._grouped(conv):
+        return False
     ci, co = conv.in_channels, conv.out_channels
     if conv.kh > 1:
         return co >= 128
@@ -479,8 +488,13 @@ class BlockFn(torch.autograd.Function):
             h_in = inputs[i]
             if i > 0:
                 bn_prev = pairs[i - 1][1]
-                fz = BNBwdFuse(acts[i - 1], bn_prev) if fuse else None
-                if isinstance(dA, GramBN):
+                grouped = _conv._grouped(conv)
+                # (a grouped conv's dgrad has no fused BN-backward epilogue: the BN before it takes the reduce pass)
+                fz = BNBwdFuse(acts[i - 1], bn_prev) if (fuse and not grouped) else None
+                if grouped:
+                    dH = gconv_dgrad(dA, conv.wt_bf16, (acts[i - 1].shape[1], acts[i - 1].shape[2]), conv.stride,
+                                     conv.groups)
+                elif isinstance(dA, GramBN):
                     dH = gram_dgrad(dA, conv, h_in, fz, Q=_gws(block, 3))
                     g_read = gram_wgrad(conv, dA, h_in, ctx.h2sum, G=_gws(block, 1), P=ctx.gram_P,
                                         bn=bn_l, T_out=_gws(block, 0), P_out=_gws(block, 4))  # issued now: it reads dout, which conv1's dgrad

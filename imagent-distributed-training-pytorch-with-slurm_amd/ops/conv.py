@@ -436,6 +436,99 @@ def _wgrad_args(dy, x, dw, stride, pad, KH, KW, stem, xbn):
     return a
 
 
+# --------------------------------------------------------------------------
+# grouped 3x3 convs (ResNeXt's conv2; conv_group.hip)
+# --------------------------------------------------------------------------
+
+def _gconv_check(x: torch.Tensor, w: torch.Tensor, groups: int, what: str) -> int:
+    Cc = x.shape[-1]
+    if groups < 1 or Cc % groups:
+        raise ValueError(f"{what}: {Cc} channels do not split into {groups} groups")
+    cg = Cc // groups
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and w.dtype == torch.bfloat16 and w.is_contiguous()
+    assert tuple(w.shape) == (Cc, 3, 3, cg), (tuple(w.shape), (Cc, 3, 3, cg))
+    return cg
+
+
+def _gconv_rc(rc: int, what: str, Cc: int, cg: int, stride: int) -> None:
+    if rc == -106:
+        raise RuntimeError(f"{what}: no grouped kernel for C={Cc}, {cg} channels per group, stride {stride} (C % 64 == "
+                           f"0, 4 / 8 / 16 / 32 / 64 channels per group, stride 1 or 2) failed with code {rc}")
+    _lib.check(rc, what)
+
+
+def gconv_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, groups: int, stats=None,
+              affine: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """y[N,OH,OW,C] = grouped 3x3 conv, pad 1, of x[N,H,W,C] with ``w`` the ``[C,3,3,C/groups]`` bf16 shadow
+    (output channel, tap, input channel within the group). ``stats`` / ``affine`` / ``relu`` as :func:`igemm_fwd`:
+    the training epilogue's BatchNorm statistics (shifted sums of the stored values into ``bn.work``'s slab; the
+    fixed-order pass in deterministic mode) or the eval epilogue. A shape the kernels do not cover raises."""
+    cg = _gconv_check(x, w, groups, "grouped conv fwd")
+    N, H, W, Cc = x.shape
+    out = torch.empty((N, conv_out_size(H, 3, stride, 1), conv_out_size(W, 3, stride, 1), Cc), device=x.device,
+                      dtype=torch.bfloat16)
+    shift, det = None, None
+    if stats is not None:
+        if hasattr(stats, "slab"):  # a BatchNorm's workspace: shifted sums around its last batch mean
+            shift = stats.save if _SHIFT else None
+            stats = stats.slab
+        if _DET:
+            det, stats, shift = (stats, shift), None, None
+    if affine is not None:
+        assert affine.shape == (2, Cc) and affine.dtype == torch.float32 and affine.is_contiguous()
+    k = _lib.kernels()
+    _gconv_rc(k.imk_gconv_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), _lib.ptr(affine), _lib.ptr(stats),
+                              _lib.ptr(shift), N, H, W, Cc, cg, stride, 1 if relu else 0, _lib.stream_ptr()),
+              "grouped conv fwd", Cc, cg, stride)
+    if det is not None:
+        _det_sync()
+        R = out.numel() // Cc
+        part = torch.empty(k.imk_bn_stats_det_floats(R, Cc), device=out.device, dtype=torch.float32)
+        _lib.check(k.imk_bn_stats_det(out.data_ptr(), _lib.ptr(det[1]), det[0].data_ptr(), part.data_ptr(), R, Cc,
+                                      _lib.stream_ptr()), "bn stats (deterministic)")
+    return out
+
+
+def gconv_dgrad(dy: torch.Tensor, wt: torch.Tensor, in_hw: Tuple[int, int], stride: int, groups: int) -> torch.Tensor:
+    """dx[N,H,W,C] = dgrad of :func:`gconv_fwd`; ``wt`` is the per-group transposed shadow ``[C,3,3,C/groups]``:
+    ``wt[g*cg + ci][ky][kx][co_in_group] = w[g*cg + co_in_group][ky][kx][ci]``. Stride 2: one launch per parity
+    class of dx with that class's taps."""
+    cg = _gconv_check(dy, wt, groups, "grouped conv dgrad")
+    N, OH, OW, Cc = dy.shape
+    H, W = in_hw
+    dx = torch.empty((N, H, W, Cc), device=dy.device, dtype=torch.bfloat16)
+    _gconv_rc(_lib.kernels().imk_gconv_dgrad(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), N, OH, OW, Cc, cg, H, W,
+                                             stride, _lib.stream_ptr()), "grouped conv dgrad", Cc, cg, stride)
+    return dx
+
+
+def gconv_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, stride: int, groups: int) -> None:
+    """dw (fp32, ``[C][3][3][C/groups]`` in memory: ``weight.grad.permute(0, 2, 3, 1)`` of a channels-last
+    ``[C,cg,3,3]`` parameter) += wgrad(dy[N,OH,OW,C], x[N,H,W,C]) by fp32 atomics over pixel ranges."""
+    N, H, W, Cc = x.shape
+    if groups < 1 or Cc % groups:
+        raise ValueError(f"grouped conv wgrad: {Cc} channels do not split into {groups} groups")
+    cg = Cc // groups
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and x.dtype == torch.bfloat16 and x.is_contiguous()
+    assert dw.dtype == torch.float32 and dw.numel() == Cc * 9 * cg and dy.shape[0] == N and dy.shape[3] == Cc
+    if dw.dim() == 4 and tuple(dw.shape) == (Cc, cg, 3, 3):
+        assert dw.permute(0, 2, 3, 1).is_contiguous(), "grouped conv wgrad: channels-last gradient storage"
+    else:
+        assert dw.is_contiguous()
+    _gconv_rc(_lib.kernels().imk_gconv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), N, H, W, Cc, cg, dy.shape[1],
+                                             dy.shape[2], stride, _lib.stream_ptr()),
+              "grouped conv wgrad", Cc, cg, stride)
+
+
+def _grouped(mod) -> bool:
+    return getattr(mod, "groups", 1) > 1
+
+
+def _gconv_mod_check(mod) -> None:
+    if not (mod.kh == 3 and mod.kw == 3 and mod.padding == 1 and mod.in_channels == mod.out_channels):
+        raise RuntimeError(f"grouped conv: only 3x3, pad 1, equal widths have a kernel (got {mod.extra_repr()})")
+
+
 def colsum_into(x2d: torch.Tensor, out: torch.Tensor) -> None:
     R, Cc = x2d.shape
     _lib.check(_lib.kernels().imk_colsum_bf16(x2d.data_ptr(), out.data_ptr(), R, Cc, _lib.stream_ptr()),
@@ -454,8 +547,12 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, mod, stats):
-        y = igemm_fwd(x, mod.w_bf16, mod.stride, mod.padding, mod.kh, mod.kw, stats=stats,
-                      stem=getattr(mod, "stem", False))
+        if _grouped(mod):
+            _gconv_mod_check(mod)
+            y = gconv_fwd(x, mod.w_bf16, mod.stride, mod.groups, stats=stats)
+        else:
+            y = igemm_fwd(x, mod.w_bf16, mod.stride, mod.padding, mod.kh, mod.kw, stats=stats,
+                          stem=getattr(mod, "stem", False))
         ctx.mod = mod
         ctx.save_for_backward(x)
         return y
@@ -467,7 +564,9 @@ class ConvFn(torch.autograd.Function):
         mod = ctx.mod
         dy = dy.contiguous()
         dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and _grouped(mod):
+            dx = gconv_dgrad(dy, mod.wt_bf16, (x.shape[1], x.shape[2]), mod.stride, mod.groups)
+        elif ctx.needs_input_grad[0]:
             dx = igemm_dgrad(dy, mod.wt_bf16, (x.shape[1], x.shape[2]), mod.stride, mod.padding, mod.kh,
                              mod.kw)
         conv_wgrad(mod, dy, x)
@@ -498,6 +597,11 @@ def conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tenso
 
 
 def _conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tensor] = None, fp8=None) -> None:
+    if _grouped(mod):  # (bf16 only: no fp8 copies, no operand-path BatchNorm)
+        assert xbn is None and fp8 is None, "grouped conv wgrad: bf16 operands only"
+        gconv_wgrad(dy, x, mod.weight.grad, mod.stride, mod.groups)
+        notify_ready(mod.weight)
+        return
     gp = getattr(mod, "grad_pad", None)
     if fp8 is not None and gp is None and xbn is None:
         dy8, e_dy, x8, e_x = fp8
