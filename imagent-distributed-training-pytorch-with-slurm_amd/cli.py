@@ -32,9 +32,14 @@ def build_parser() -> argparse.ArgumentParser:
     # --- model / data ---
     p.add_argument("--arch", default="resnet18", choices=["resnet18", "resnet34", "resnet50", "resnet101",
                                                            "resnet152", "resnext50_32x4d", "resnext101_32x8d",
-                                                           "resnext101_64x4d"],
+                                                           "resnext101_64x4d", "seresnet18", "seresnet34",
+                                                           "seresnet50", "seresnet101", "seresnet152",
+                                                           "seresnext50_32x4d", "seresnext101_32x8d",
+                                                           "seresnext101_64x4d"],
                    help="resnext*: grouped bottlenecks (conv2 on the grouped HIP kernels, bf16; --dtype fp8 keeps "
-                        "those convs bf16; not with --dtype fp32 on the HIP kernels)")
+                        "those convs bf16; not with --dtype fp32 on the HIP kernels). se*: a squeeze-and-excitation "
+                        "gate at the end of each block (block tail on the HIP kernels of ops/se.py; --dtype bf16 "
+                        "only on the HIP kernels)")
     p.add_argument("--image-size", type=int, default=448)
     p.add_argument("--deterministic", action="store_true",
                    help="BatchNorm statistics without float atomics (fixed-order reduction passes): two runs "

@@ -24,6 +24,7 @@ from ..ops import _lib
 from ..ops.block import BlockFn
 from ..ops.bn import BNActFn, bn_eval, running_update
 from ..ops.conv import ConvFn, LinearFn, conv_out_size, deterministic, gconv_fwd, igemm_fwd
+from ..ops.se import SETailFn, se_gate_eval
 from ..ops.misc import AvgPoolFn, BNReluPoolFn, MaxPoolFn, StemFn, TransposePlan, maxpool_eval, stem_fused_ok
 from .arena import ParamArena
 from .resnet import BasicBlock, BatchNorm2d, BNWork, Bottleneck, Conv2d, Linear, ResNet
@@ -39,6 +40,8 @@ class NativeState:
     def __init__(self, model: ResNet, device: torch.device, order: Optional[Sequence[int]] = None,
                  bnb_fusion: bool = True, fp8: bool = False, wgrad_overlap: bool = True, fp8_wgrad: bool = False):
         self.device = torch.device(device)
+        if fp8 and getattr(model, "se", False):
+            raise ValueError("the squeeze-and-excitation archs run bf16 on the HIP kernels: no fp8 path")
         named = list(model.named_parameters())
         self.arena = ParamArena(named, self.device, order=order, with_shadow=True)
         self.model = model
@@ -112,6 +115,9 @@ class NativeState:
             c.grad_pad = None
             if c is not m.conv1:
                 t_numel += sh.numel()
+        for b in m.blocks():  # the SE gates read their weights' bf16 shadows as they lie: fc1 [R][C], fc2 [C][R]
+            if getattr(b, "se", None) is not None:
+                b.se.fc1.w_bf16, b.se.fc2.w_bf16 = ar.shadow(b.se.fc1.weight), ar.shadow(b.se.fc2.weight)
         fc: Linear = m.fc
         fc.w_bf16 = ar.shadow(fc.weight).view(fc.out_features, fc.in_features)
         t_numel += fc.w_bf16.numel()
@@ -416,7 +422,14 @@ def forward_hip(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         conv, bn, _ = pairs[-1]
         a = _conv(out, conv, bn, train)
         rows.append(a.numel() // a.shape[-1])
-        if b.downsample is not None:
+        if getattr(b, "se", None) is not None:  # (training: forward_hip returns through _forward_eval otherwise)
+            if b.downsample is not None:
+                dconv, dbn = b.downsample[0], b.downsample[1]
+                ad = _conv(idt, dconv, dbn, train)
+                rows.append(ad.numel() // ad.shape[-1])
+                idt = _bn(ad, dbn, False, train)
+            y = SETailFn.apply(a, idt, bn, b.se)
+        elif b.downsample is not None:
             dconv, dbn = b.downsample[0], b.downsample[1]
             ad = _conv(idt, dconv, dbn, train)
             rows.append(ad.numel() // ad.shape[-1])
@@ -448,7 +461,8 @@ def _forward_eval(model: ResNet, x: torch.Tensor) -> torch.Tensor:
     """Inference: every BatchNorm (+ReLU, +residual) folded into the epilogue
     of the conv that feeds it -- one pass per conv, no BN kernels.
     The block's last conv accumulates onto the shortcut (identity copy or the
-    downsample conv's folded output) and applies the ReLU after the sum."""
+    downsample conv's folded output) and applies the ReLU after the sum; in an SE block it writes the BatchNorm
+    output and the gate, the shortcut add and the ReLU follow as one pass."""
     st = getattr(model, "native", None)
     st = st if isinstance(st, NativeState) else None
     if st is not None:
@@ -473,6 +487,11 @@ def _forward_eval(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         # the block's last conv accumulates onto the shortcut: the downsample conv's output, or the block
         # input itself, in place (no later reader: every consumer of y in this block has run)
         short = conv(y, b.downsample[0], b.downsample[1], False) if b.downsample is not None else y
+        if getattr(b, "se", None) is not None:
+            # an SE block: the folded affine without ReLU or accumulate gives u; the gate from u, applied with the
+            # shortcut add and the ReLU in one pass (ops/se.py)
+            y = se_gate_eval(conv(h, c, bn, False), short, b.se)
+            continue
         y = conv(h, c, bn, True, out=short, accumulate=True)
     pooled = _avg_eval(y)
     fc = model.fc

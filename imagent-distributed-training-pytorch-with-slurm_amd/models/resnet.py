@@ -1,4 +1,6 @@
-"""ResNet-18/34/50/101/152 and ResNeXt-50 32x4d / -101 32x8d / -101 64x4d with torchvision-identical parameter names.
+"""ResNet-18/34/50/101/152 and ResNeXt-50 32x4d / -101 32x8d / -101 64x4d with torchvision-identical parameter names,
+and their squeeze-and-excitation variants (``seresnet*`` / ``seresnext*``: a channel gate ``se`` after each block's
+last BatchNorm, parameter names ``layerL.i.se.fc1.weight`` .. as in timm).
 
 The reference instantiates ``torchvision.models.resnet18(pretrained=False,
 num_classes=1000)`` (``/root/reference/imagenet.py:312``); torchvision is not
@@ -99,6 +101,34 @@ class Linear(nn.Module):
         return F.linear(x, self.weight.to(x.dtype), self.bias.to(x.dtype))
 
 
+class SEConv(nn.Module):
+    """One 1x1 conv with bias of the SE gate: parameters only. Deliberately not a :class:`Conv2d`: ``ResNet.convs()``,
+    the dgrad transpose plan, the fp8 quantiser and ``conv_wgrad`` never see it (ops/se.py runs the gate)."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        w = torch.empty(cout, cin, 1, 1)
+        nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu")
+        self.weight = nn.Parameter(w)
+        self.bias = nn.Parameter(torch.zeros(cout))
+        self.w_bf16: Optional[torch.Tensor] = None  # [cout * cin] bf16 shadow bound by ResNet.bind_native()
+
+
+class SEModule(nn.Module):
+    """Squeeze-and-excitation gate: s = sigmoid(fc2(relu(fc1(mean_hw x)))), R = max(8, C // 16) reduced channels."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        self.channels, self.reduced = channels, max(8, channels // 16)
+        self.fc1 = SEConv(channels, self.reduced)
+        self.fc2 = SEConv(self.reduced, channels)
+
+    def forward_torch(self, x):
+        z = x.mean((2, 3), keepdim=True)
+        h = F.relu(F.conv2d(z, self.fc1.weight.to(x.dtype), self.fc1.bias.to(x.dtype)))
+        return x * torch.sigmoid(F.conv2d(h, self.fc2.weight.to(x.dtype), self.fc2.bias.to(x.dtype)))
+
+
 class BNWork:
     """Per-BN device workspace (views into one arena zeroed once per step)."""
 
@@ -117,7 +147,7 @@ class BNWork:
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64, se=False):
         super().__init__()
         if groups != 1 or width_per_group != 64:
             raise ValueError("BasicBlock only supports groups=1 and width_per_group=64")
@@ -125,6 +155,7 @@ class BasicBlock(nn.Module):
         self.bn1 = BatchNorm2d(planes)
         self.conv2 = Conv2d(planes, planes, 3, 1, 1)
         self.bn2 = BatchNorm2d(planes)
+        self.se = SEModule(planes) if se else None
         self.downsample = downsample
         self.stride = stride
 
@@ -134,6 +165,8 @@ class BasicBlock(nn.Module):
     def forward_torch(self, x):
         out = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
         out = self.bn2.forward_torch(self.conv2.forward_torch(out))
+        if self.se is not None:
+            out = self.se.forward_torch(out)
         idt = x if self.downsample is None else \
             self.downsample[1].forward_torch(self.downsample[0].forward_torch(x))
         return F.relu(out + idt)
@@ -142,7 +175,7 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64, se=False):
         super().__init__()
         width = int(planes * width_per_group / 64) * groups  # torchvision's rule (ResNeXt: groups > 1)
         self.conv1 = Conv2d(inplanes, width, 1)
@@ -151,6 +184,7 @@ class Bottleneck(nn.Module):
         self.bn2 = BatchNorm2d(width)
         self.conv3 = Conv2d(width, planes * 4, 1)
         self.bn3 = BatchNorm2d(planes * 4)
+        self.se = SEModule(planes * 4) if se else None
         self.downsample = downsample
         self.stride = stride
 
@@ -161,6 +195,8 @@ class Bottleneck(nn.Module):
         out = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
         out = F.relu(self.bn2.forward_torch(self.conv2.forward_torch(out)))
         out = self.bn3.forward_torch(self.conv3.forward_torch(out))
+        if self.se is not None:
+            out = self.se.forward_torch(out)
         idt = x if self.downsample is None else \
             self.downsample[1].forward_torch(self.downsample[0].forward_torch(x))
         return F.relu(out + idt)
@@ -177,10 +213,10 @@ class ResNet(nn.Module):
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: List[int],
                  num_classes: int = 1000, zero_init_residual: bool = False, groups: int = 1,
-                 width_per_group: int = 64):
+                 width_per_group: int = 64, se: bool = False):
         super().__init__()
         self.block = block
-        self.groups, self.width_per_group = groups, width_per_group
+        self.groups, self.width_per_group, self.se = groups, width_per_group, se
         self.inplanes = 64
         self.conv1 = Conv2d(3, 64, 7, 2, 3)
         self.bn1 = BatchNorm2d(64)
@@ -203,7 +239,7 @@ class ResNet(nn.Module):
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride),
                                        BatchNorm2d(planes * block.expansion))
-        gw = dict(groups=self.groups, width_per_group=self.width_per_group)
+        gw = dict(groups=self.groups, width_per_group=self.width_per_group, se=self.se)
         layers = [block(self.inplanes, planes, stride, downsample, **gw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
@@ -277,11 +313,20 @@ def resnext101_64x4d(**kw) -> ResNet:
     return _resnet(Bottleneck, [3, 4, 23, 3], groups=64, width_per_group=4, **kw)
 
 
+def _se(fn: Callable[..., ResNet]) -> Callable[..., ResNet]:
+    return lambda **kw: fn(se=True, **kw)
+
+
 ARCHS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101,
          "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d, "resnext101_32x8d": resnext101_32x8d,
          "resnext101_64x4d": resnext101_64x4d}
+ARCHS.update({"se" + name: _se(fn) for name, fn in list(ARCHS.items())})
 # the grouped-bottleneck archs: bf16 HIP kernels (ops/conv.py gconv_*) or the torch backend, no fp32 HIP path
-GROUPED_ARCHS = ("resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d")
+GROUPED_ARCHS = ("resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d",
+                 "seresnext50_32x4d", "seresnext101_32x8d", "seresnext101_64x4d")
+# the squeeze-and-excitation archs: bf16 HIP kernels (ops/se.py) or the torch backend, no fp8 / fp32 HIP path
+SE_ARCHS = ("seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
+            "seresnext50_32x4d", "seresnext101_32x8d", "seresnext101_64x4d")
 
 
 def build(arch: str, num_classes: int = 1000, **kw) -> ResNet:

@@ -166,6 +166,13 @@ def _declare(name: str, lib) -> None:
             "imk_gconv_fwd": [vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp],
             "imk_gconv_dgrad": [vp, vp, vp] + [i32] * 8 + [vp],
             "imk_gconv_wgrad": [vp, vp, vp] + [i32] * 8 + [vp],
+            # squeeze-and-excitation block tail (se.hip)
+            "imk_se_squeeze": [vp, vp, vp, i32, i32, i32, vp],
+            "imk_se_bwd_reduce": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+            "imk_se_excite_fwd": [vp] * 9 + [i32, i32, i32, i32, vp],
+            "imk_se_scale_add_relu": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
+            "imk_se_excite_bwd": [vp] * 18 + [i32, i32, i32, i32, vp],
+            "imk_se_bn_apply_bwd": [vp] * 8 + [i32, i32, i32, vp],
             "imk_probe_ds_read_tr8": [vp, i32, vp, vp],
             "imk_conv_launches": [],
             # fp32 path (f32.hip)
@@ -254,6 +261,10 @@ def _declare(name: str, lib) -> None:
             f.restype = C.c_int
         lib.imk_bn_stats_det_floats.argtypes = [i64, i32]
         lib.imk_bn_stats_det_floats.restype = C.c_long
+        lib.imk_se_reduce_floats.argtypes = [i32, i32, i32, i32]
+        lib.imk_se_reduce_floats.restype = C.c_long
+        lib.imk_se_excite_bwd_floats.argtypes = [i32, i32, i32]
+        lib.imk_se_excite_bwd_floats.restype = C.c_long
         # ABI guard: the ctypes mirrors must match the compiled structs
         for fn, st in [("imk_igemm_args_size", IGemmArgs), ("imk_wgrad_args_size", WgradArgs),
                        ("imk_bn_rundesc_size", RunDesc), ("imk_bn_affdesc_size", AffDesc), ("imk_tdesc_size", TDesc),

@@ -36,6 +36,7 @@ from . import conv as _conv
 from .bn import bn_act_backward, bn_act_forward, bn_apply_backward, bn_scale_shift
 from .bn_gram import GramBN, gram_T, gram_coef, gram_dgrad, gram_fwd_stats, gram_wgrad
 from .conv import BNBwdFuse, conv_wgrad, gconv_dgrad, gconv_fwd, igemm_dgrad, igemm_fwd
+from .se import se_tail_backward, se_tail_forward
 
 
 # Each weight gradient is issued after the BN-backward pass that follows its dgrad, so the side stream's wgrad
@@ -124,6 +125,8 @@ def _take_T(block, dout, h2):
 def _next1_target(block, conv, q):
     """The next block's (conv1, bn1) when conv3's fused-output launch can compute that conv too, else None."""
     nb = getattr(block, "_next_block", None)
+    if getattr(block, "se", None) is not None:  # an SE block's tail is not conv3's epilogue
+        return None
     if not _NEXT1 or nb is None or q is not None or _conv.deterministic():
         return None
     c1, b1, _ = nb.convs_bns()[0]
@@ -137,6 +140,8 @@ def _next1_target(block, conv, q):
 def _gram_ok(block, q, x) -> bool:
     """Does this block's backward take bn3 through the Gram form (forward keeps h2)?"""
     pairs = block.convs_bns()
+    if getattr(block, "se", None) is not None:  # the gate sits between bn3 and the shortcut add (ops/se.py)
+        return False
     if not (_GRAM and x.is_cuda and len(pairs) == 3):  # (with fp8: conv3's dgrad stays bf16 in this form)
         return False
     if _conv.deterministic():  # split-K atomics accumulate G / T: never on the bit-identical statistics path
@@ -324,7 +329,9 @@ class BlockFn(torch.autograd.Function):
             h8 = (q8[0], q8[1]) if q8 is not None else None
             saved += [a, h]
         conv, bn, _ = pairs[-1]
-        fuse_next = getattr(block, "_fuse_bnb", False)
+        se = getattr(block, "se", None)
+        # an SE block: its last BatchNorm is finished by its own tail (ops/se.py), never by the next block's dgrad
+        fuse_next = getattr(block, "_fuse_bnb", False) and se is None
         # the block output's e4m3 copy only when the next block's conv1 or downsample conv reads fp8
         need8 = q is not None and getattr(block, "_q8_out", True)
         gws = getattr(block, "_gram_ws", None)
@@ -374,8 +381,21 @@ class BlockFn(torch.autograd.Function):
             # the ReLU mask of the block output as bits, for the next block's conv1 dgrad epilogue (1/16
             # of the bytes of re-reading the output there)
             ym = torch.empty(a.numel() // 8, device=a.device, dtype=torch.uint8) if fuse_next else None
+        se_state = None
         if fused3:
             pass
+        elif se is not None:
+            # relu(s * bn(a) + shortcut): a downsample block first materialises its shortcut (mode 0, no ReLU)
+            if ds is not None:
+                if side is not None:
+                    cur = torch.cuda.current_stream()
+                    streams.wait(cur, side)
+                    ad.record_stream(cur)
+                else:
+                    ad = _fwd8(ds[0], x, x8, ds[1])
+            idt = bn_act_forward(ad, None, ds[1], None, 0, False) if ds is not None else x
+            out, se_state = se_tail_forward(a, bn, idt, se)
+            se_state = se_state[2:]
         elif ds is not None:
             if side is not None:
                 cur = torch.cuda.current_stream()
@@ -406,6 +426,7 @@ class BlockFn(torch.autograd.Function):
         ctx.wg8 = wg8 or None
         ctx.gram = gram
         ctx.h2sum = h2sum
+        ctx.se_state = se_state  # (ss, X1, z, h, s) of an SE block's tail
         ctx.gram_P = gram_P  # W3 G from the fused forward (G in the block's workspace): not recomputed
         block._gram = gram  # the next block's conv1 dgrad may then skip reading x3 (BNBwdFuse without x)
         block._bnb_nox = False
@@ -437,7 +458,12 @@ class BlockFn(torch.autograd.Function):
         dA8 = None
         sparse = False
         if ds is not None:
-            if premasked and ctx.gram and fuse:
+            if ctx.se_state is not None:
+                # the SE tail; its g is the gradient of the materialised shortcut bn_d(ad) (mode 0, no ReLU)
+                dA, g = se_tail_backward(dout, (a_last, out) + tuple(ctx.se_state), bn_l, block.se)
+                dAd, _ = bn_act_backward(g, ad, None, None, ds[1], None, 0, False)
+                dAd8 = None
+            elif premasked and ctx.gram and fuse:
                 # bn3 in the Gram form (as for identity blocks below); the downsample BN alone gets an apply pass:
                 # its reductions (sum g, sum g xhat_d) sit in bn3's slab rows 1, 2 (read there, sgx_row=2)
                 T = _take_T(block, dout, outs[-1])
@@ -462,6 +488,8 @@ class BlockFn(torch.autograd.Function):
                 conv_wgrad(dconv, dAd, x, fp8=_wg8(dAd8, wg8.get("ds")))
             else:
                 conv_wgrad(dconv, dAd, x)
+        elif ctx.se_state is not None:
+            dA, dX = se_tail_backward(dout, (a_last, out) + tuple(ctx.se_state), bn_l, block.se)  # dX = masked dout
         elif premasked and ctx.gram and fuse:
             # dx3 kept as (g, A, B, c): no apply pass (ops/bn_gram.py); when the next block's dgrad ran without x3,
             # sum(g xhat3) comes from T = g^T h2 (formed here, reused by the weight gradient)

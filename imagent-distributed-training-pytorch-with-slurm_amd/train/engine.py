@@ -250,7 +250,10 @@ class Trainer:
         if getattr(a, "fp8_wgrad", False) and (a.dtype != "fp8" or a.kernels == "torch"):
             raise SystemExit("--fp8-wgrad needs --dtype fp8 --kernels hip (the fp8 weight gradient reads the 1-byte "
                              f"copies of the fp8 forward and dgrad): got --dtype {a.dtype} --kernels {a.kernels}")
-        from ..models.resnet import GROUPED_ARCHS
+        from ..models.resnet import GROUPED_ARCHS, SE_ARCHS
+        if a.arch in SE_ARCHS and a.dtype != "bf16" and a.kernels != "torch":
+            raise SystemExit(f"--arch {a.arch} with --dtype {a.dtype}: the squeeze-and-excitation block tail has "
+                             "bf16 HIP kernels only; use --dtype bf16, or --kernels torch")
         if a.arch in GROUPED_ARCHS and a.dtype == "fp32" and a.kernels != "torch":
             raise SystemExit(f"--arch {a.arch} with --dtype fp32: the fp32 HIP kernels have no grouped convolution; "
                              "use --dtype bf16 (or fp8), or --kernels torch")
