@@ -35,11 +35,18 @@ def build_parser() -> argparse.ArgumentParser:
                                                            "resnext101_64x4d", "seresnet18", "seresnet34",
                                                            "seresnet50", "seresnet101", "seresnet152",
                                                            "seresnext50_32x4d", "seresnext101_32x8d",
-                                                           "seresnext101_64x4d"],
+                                                           "seresnext101_64x4d", "resnet18d", "resnet34d", "resnet50d",
+                                                           "resnet101d", "resnet152d", "resnext50d_32x4d",
+                                                           "resnext101d_32x8d", "resnext101d_64x4d", "seresnet18d",
+                                                           "seresnet34d", "seresnet50d", "seresnet101d", "seresnet152d",
+                                                           "seresnext50d_32x4d", "seresnext101d_32x8d",
+                                                           "seresnext101d_64x4d"],
                    help="resnext*: grouped bottlenecks (conv2 on the grouped HIP kernels, bf16; --dtype fp8 keeps "
                         "those convs bf16; not with --dtype fp32 on the HIP kernels). se*: a squeeze-and-excitation "
                         "gate at the end of each block (block tail on the HIP kernels of ops/se.py; --dtype bf16 "
-                        "only on the HIP kernels)")
+                        "only on the HIP kernels). *d (resnet50d, resnext50d_32x4d, ..): ResNet-D, a deep 3x3 stem and an "
+                        "average-pool shortcut (ops/conv.py nconv_*, ops/misc.py avgpool2_*; --dtype bf16 only on the HIP "
+                        "kernels)")
     p.add_argument("--image-size", type=int, default=448)
     p.add_argument("--deterministic", action="store_true",
                    help="BatchNorm statistics without float atomics (fixed-order reduction passes): two runs "

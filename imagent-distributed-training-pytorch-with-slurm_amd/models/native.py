@@ -23,9 +23,9 @@ import torch
 from ..ops import _lib
 from ..ops.block import BlockFn
 from ..ops.bn import BNActFn, bn_eval, running_update
-from ..ops.conv import ConvFn, LinearFn, conv_out_size, deterministic, gconv_fwd, igemm_fwd
+from ..ops.conv import ConvFn, LinearFn, _narrow_act, conv_out_size, deterministic, gconv_fwd, igemm_fwd, nconv_fwd
 from ..ops.se import SETailFn, se_gate_eval
-from ..ops.misc import AvgPoolFn, BNReluPoolFn, MaxPoolFn, StemFn, TransposePlan, maxpool_eval, stem_fused_ok
+from ..ops.misc import AvgPool2Fn, AvgPoolFn, BNReluPoolFn, avgpool2_fwd, MaxPoolFn, StemFn, TransposePlan, maxpool_eval, stem_fused_ok
 from .arena import ParamArena
 from .resnet import BasicBlock, BatchNorm2d, BNWork, Bottleneck, Conv2d, Linear, ResNet
 
@@ -42,6 +42,8 @@ class NativeState:
         self.device = torch.device(device)
         if fp8 and getattr(model, "se", False):
             raise ValueError("the squeeze-and-excitation archs run bf16 on the HIP kernels: no fp8 path")
+        if fp8 and getattr(model, "deep", False):
+            raise ValueError("the ResNet-D archs run bf16 on the HIP kernels: no fp8 path")
         named = list(model.named_parameters())
         self.arena = ParamArena(named, self.device, order=order, with_shadow=True)
         self.model = model
@@ -87,7 +89,7 @@ class NativeState:
         blocks = list(self.model.blocks())
 
         def reads8(b):
-            return fp8_fwd_ok(b.conv1) or (b.downsample is not None and fp8_fwd_ok(b.downsample[0]))
+            return fp8_fwd_ok(b.conv1) or (b.downsample is not None and fp8_fwd_ok(b.shortcut().conv))
         for k, b in enumerate(blocks):
             b._q8_out = k + 1 < len(blocks) and reads8(blocks[k + 1])
             # does a BatchNorm-backward pass write the e5m2 copy of each conv's output gradient? Only the fused
@@ -98,7 +100,7 @@ class NativeState:
             for i, (c, _, _) in enumerate(pairs):
                 c._g8_copy = self.bnb_fusion and not (last and i + 1 == len(pairs))
             if b.downsample is not None:
-                b.downsample[0]._g8_copy = self.bnb_fusion and not last
+                b.shortcut().conv._g8_copy = self.bnb_fusion and not last
         self._q8_pool = bool(blocks) and reads8(blocks[0])
 
     # ------------------------------------------------------------ shadows
@@ -108,12 +110,13 @@ class NativeState:
         st_items = []
         t_numel = 0
         convs: List[Conv2d] = m.convs()
+        first = m.stem()[0][0]  # the conv on the image: no input gradient, no transposed shadow
         for c in convs:
             # (a grouped conv: [C][3][3][cg], output channel x tap x input channel within the group)
             sh = ar.shadow(c.weight).view(c.out_channels, c.kh, c.kw, c.in_channels // c.groups)
             c.w_bf16 = sh
             c.grad_pad = None
-            if c is not m.conv1:
+            if c is not first:
                 t_numel += sh.numel()
         for b in m.blocks():  # the SE gates read their weights' bf16 shadows as they lie: fc1 [R][C], fc2 [C][R]
             if getattr(b, "se", None) is not None:
@@ -124,7 +127,7 @@ class NativeState:
         self.T = torch.empty(t_numel, dtype=torch.bfloat16, device=dev)
         off = 0
         for c in convs:
-            if c is m.conv1:
+            if c is first:
                 continue
             n = c.w_bf16.numel()
             if c.groups > 1:
@@ -146,6 +149,8 @@ class NativeState:
         fc.wt_bf16 = self.T[off:off + n].view(fc.in_features, fc.out_features)
         st_items.append((fc.w_bf16, fc.wt_bf16, fc.out_features, 1, fc.in_features))
         self.tplan = TransposePlan(st_items, dev)
+        if m.deep:  # the narrow kernels read the [32][3][3][3] shadow as it lies (ops/conv.py nconv_fwd)
+            return
         # stem: input channels 3 -> 4, kernel row = 7 taps x 4 ch padded to 32
         s = m.conv1
         s.stem = True
@@ -162,9 +167,11 @@ class NativeState:
         if full:
             cast_bf16(self.arena.P, self.arena.S)
         self.tplan.run()
-        s = self.model.conv1
-        src = s.w_bf16_real
-        if src.is_cuda and src.is_contiguous():
+        s = self.model.stem()[0][0]
+        src = getattr(s, "w_bf16_real", None)
+        if src is None:  # (the deep stem: no padded copy)
+            pass
+        elif src.is_cuda and src.is_contiguous():
             _lib.check(_lib.kernels().imk_stem_pad(src.data_ptr(), s.w_pad.data_ptr(), s.out_channels, s.kh, s.kw,
                                                    s.in_channels, _lib.stream_ptr()), "stem pad")
         else:
@@ -355,6 +362,8 @@ def _conv(x, conv: Conv2d, bn: Optional[BatchNorm2d], train: bool):
         return ConvFn.apply(x, conv.weight, conv, bn.work if bn is not None else None)
     if conv.groups > 1:
         return gconv_fwd(x, conv.w_bf16, conv.stride, conv.groups)
+    if _narrow_act(conv):
+        return nconv_fwd(x, conv.w_bf16, conv.stride)
     return igemm_fwd(x, conv.w_bf16, conv.stride, conv.padding, conv.kh, conv.kw,
                      stem=getattr(conv, "stem", False))
 
@@ -385,7 +394,22 @@ def forward_hip(model: ResNet, x: torch.Tensor) -> torch.Tensor:
     if not train:
         return _forward_eval(model, x)
     rows = []
-    if _FUSED_STEM and not deterministic() and stem_fused_ok(x, model.conv1):
+    stem = model.stem()
+    for conv, bn in stem[:-1]:  # the deep stem's first two convs: conv -> BN + ReLU as separate nodes
+        x = _conv(x, conv, bn, train)
+        rows.append(x.numel() // x.shape[-1])
+        x = _bn(x, bn, True, train)
+    c_last = stem[-1][0]
+    if model.deep and _FUSED_STEM and not deterministic():  # BN + ReLU inside the max-pool, as below
+        y = _conv(x, c_last, model.bn1, train)
+        rows.append(y.numel() // y.shape[-1])
+        y = BNReluPoolFn.apply(y, model.bn1, 3, 2, 1)
+    elif model.deep:
+        y = _conv(x, c_last, model.bn1, train)
+        rows.append(y.numel() // y.shape[-1])
+        y = _bn(y, model.bn1, True, train)
+        y = MaxPoolFn.apply(y, 3, 2, 1)
+    elif _FUSED_STEM and not deterministic() and stem_fused_ok(x, model.conv1):
         # conv + BN + ReLU + maxpool as one node: the stem BN's backward apply rides in the stem weight gradient
         # (ops.misc.StemFn; same-box in-step A/B 17,061 / 17,085 vs 16,809 / 16,873 img/s at 2048 img/GPU)
         c1 = model.conv1
@@ -424,14 +448,16 @@ def forward_hip(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         rows.append(a.numel() // a.shape[-1])
         if getattr(b, "se", None) is not None:  # (training: forward_hip returns through _forward_eval otherwise)
             if b.downsample is not None:
-                dconv, dbn = b.downsample[0], b.downsample[1]
-                ad = _conv(idt, dconv, dbn, train)
+                sc = b.shortcut()
+                dconv, dbn = sc.conv, sc.bn
+                ad = _conv(AvgPool2Fn.apply(idt) if sc.pool is not None else idt, dconv, dbn, train)
                 rows.append(ad.numel() // ad.shape[-1])
                 idt = _bn(ad, dbn, False, train)
             y = SETailFn.apply(a, idt, bn, b.se)
         elif b.downsample is not None:
-            dconv, dbn = b.downsample[0], b.downsample[1]
-            ad = _conv(idt, dconv, dbn, train)
+            sc = b.shortcut()
+            dconv, dbn = sc.conv, sc.bn
+            ad = _conv(AvgPool2Fn.apply(idt) if sc.pool is not None else idt, dconv, dbn, train)
             rows.append(ad.numel() // ad.shape[-1])
             y = _bn(a, bn, True, train, x2=ad, bn2=dbn, mode=2)
         else:
@@ -473,10 +499,15 @@ def _forward_eval(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         if c.groups > 1:  # (never a block's last conv: no shortcut to accumulate onto)
             assert out is None and not accumulate
             return gconv_fwd(h, c.w_bf16, c.stride, c.groups, affine=aff, relu=relu)
+        if _narrow_act(c):  # (the deep stem's first two convs)
+            assert out is None and not accumulate
+            return nconv_fwd(h, c.w_bf16, c.stride, affine=aff, relu=relu)
         return igemm_fwd(h, c.w_bf16, c.stride, c.padding, c.kh, c.kw, stem=getattr(c, "stem", False),
                          affine=aff, relu=relu, out=out, accumulate=accumulate)
 
-    y = conv(x, model.conv1, model.bn1, True)
+    y = x
+    for c, bn in model.stem():
+        y = conv(y, c, bn, True)
     y = maxpool_eval(y, 3, 2, 1)
     for b in model.blocks():
         pairs = b.convs_bns()
@@ -486,7 +517,8 @@ def _forward_eval(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         c, bn, _ = pairs[-1]
         # the block's last conv accumulates onto the shortcut: the downsample conv's output, or the block
         # input itself, in place (no later reader: every consumer of y in this block has run)
-        short = conv(y, b.downsample[0], b.downsample[1], False) if b.downsample is not None else y
+        sc = b.shortcut()  # (the D archs: pool -> folded conv)
+        short = y if sc is None else conv(avgpool2_fwd(y) if sc.pool is not None else y, sc.conv, sc.bn, False)
         if getattr(b, "se", None) is not None:
             # an SE block: the folded affine without ReLU or accumulate gives u; the gate from u, applied with the
             # shortcut add and the ReLU in one pass (ops/se.py)
@@ -511,6 +543,6 @@ def _avg_eval(y):
 
 def _rows_in_bn_order(model: ResNet, rows_fwd: List[int]) -> List[int]:
     """Map the per-conv row counts (forward order) onto model.batchnorms() order."""
-    # forward order: stem, then per block conv1..convK, [downsample]; batchnorms()
-    # (module order) lists: bn1, then per block bn1..bnK, [downsample.1] -> identical.
+    # forward order: stem (the deep stem: its three convs), then per block conv1..convK, [downsample]; batchnorms()
+    # (module order) lists: [conv1.1, conv1.4,] bn1, then per block bn1..bnK, [downsample.1 / .2] -> identical.
     return rows_fwd

@@ -1,6 +1,9 @@
 """ResNet-18/34/50/101/152 and ResNeXt-50 32x4d / -101 32x8d / -101 64x4d with torchvision-identical parameter names,
 and their squeeze-and-excitation variants (``seresnet*`` / ``seresnext*``: a channel gate ``se`` after each block's
-last BatchNorm, parameter names ``layerL.i.se.fc1.weight`` .. as in timm).
+last BatchNorm, parameter names ``layerL.i.se.fc1.weight`` .. as in timm), and the ResNet-D variants of all of them
+(``resnet50d``, ``resnext50d_32x4d``, ``seresnet50d`` ..: timm's ``stem_type='deep', stem_width=32, avg_down=True`` --
+``conv1`` is a Sequential of three 3x3 convs, a downsampling shortcut is pool -> 1x1 stride-1 conv -> BN under
+``downsample.0/.1/.2``).
 
 The reference instantiates ``torchvision.models.resnet18(pretrained=False,
 num_classes=1000)`` (``/root/reference/imagenet.py:312``); torchvision is not
@@ -129,6 +132,30 @@ class SEModule(nn.Module):
         return x * torch.sigmoid(F.conv2d(h, self.fc2.weight.to(x.dtype), self.fc2.bias.to(x.dtype)))
 
 
+class AvgPool2(nn.Module):
+    """The ResNet-D shortcut's pool: ``AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False)``; no parameters."""
+
+    def forward_torch(self, x):
+        return F.avg_pool2d(x, 2, 2, ceil_mode=True, count_include_pad=False)
+
+
+class Shortcut:
+    """A downsampling block's shortcut as its parts, whatever their indices in ``downsample``: ``pool`` (the D archs'
+    2x2 average pool in front of the conv, or None), the 1x1 ``conv`` and its BatchNorm ``bn``."""
+
+    __slots__ = ("pool", "conv", "bn")
+
+    def __init__(self, seq: nn.Sequential):
+        # torchvision: downsample.0 conv, .1 BN; the D archs (timm avg_down): .0 pool / identity, .1 conv, .2 BN
+        self.conv, self.bn = seq[-2], seq[-1]
+        self.pool = seq[0] if isinstance(seq[0], AvgPool2) else None
+
+    def forward_torch(self, x):
+        if self.pool is not None:
+            x = self.pool.forward_torch(x)
+        return self.bn.forward_torch(self.conv.forward_torch(x))
+
+
 class BNWork:
     """Per-BN device workspace (views into one arena zeroed once per step)."""
 
@@ -162,13 +189,15 @@ class BasicBlock(nn.Module):
     def convs_bns(self):
         return [(self.conv1, self.bn1, True), (self.conv2, self.bn2, False)]
 
+    def shortcut(self) -> Optional["Shortcut"]:
+        return None if self.downsample is None else Shortcut(self.downsample)
+
     def forward_torch(self, x):
         out = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
         out = self.bn2.forward_torch(self.conv2.forward_torch(out))
         if self.se is not None:
             out = self.se.forward_torch(out)
-        idt = x if self.downsample is None else \
-            self.downsample[1].forward_torch(self.downsample[0].forward_torch(x))
+        idt = x if self.downsample is None else self.shortcut().forward_torch(x)
         return F.relu(out + idt)
 
 
@@ -191,14 +220,16 @@ class Bottleneck(nn.Module):
     def convs_bns(self):
         return [(self.conv1, self.bn1, True), (self.conv2, self.bn2, True), (self.conv3, self.bn3, False)]
 
+    def shortcut(self) -> Optional["Shortcut"]:
+        return None if self.downsample is None else Shortcut(self.downsample)
+
     def forward_torch(self, x):
         out = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
         out = F.relu(self.bn2.forward_torch(self.conv2.forward_torch(out)))
         out = self.bn3.forward_torch(self.conv3.forward_torch(out))
         if self.se is not None:
             out = self.se.forward_torch(out)
-        idt = x if self.downsample is None else \
-            self.downsample[1].forward_torch(self.downsample[0].forward_torch(x))
+        idt = x if self.downsample is None else self.shortcut().forward_torch(x)
         return F.relu(out + idt)
 
 
@@ -213,12 +244,18 @@ class ResNet(nn.Module):
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: List[int],
                  num_classes: int = 1000, zero_init_residual: bool = False, groups: int = 1,
-                 width_per_group: int = 64, se: bool = False):
+                 width_per_group: int = 64, se: bool = False, deep: bool = False):
         super().__init__()
         self.block = block
         self.groups, self.width_per_group, self.se = groups, width_per_group, se
+        # ResNet-D (timm stem_type='deep', stem_width=32, avg_down=True): three 3x3 stem convs, pooled shortcuts
+        self.deep = deep
         self.inplanes = 64
-        self.conv1 = Conv2d(3, 64, 7, 2, 3)
+        if deep:  # (indices 2 and 5: the parameter-free ReLUs of timm's Sequential)
+            self.conv1 = nn.Sequential(Conv2d(3, 32, 3, 2, 1), BatchNorm2d(32), nn.ReLU(), Conv2d(32, 32, 3, 1, 1),
+                                       BatchNorm2d(32), nn.ReLU(), Conv2d(32, 64, 3, 1, 1))
+        else:
+            self.conv1 = Conv2d(3, 64, 7, 2, 3)
         self.bn1 = BatchNorm2d(64)
         self.layer1 = self._make_layer(block, 64, layers[0])
         self.layer2 = self._make_layer(block, 128, layers[1], 2)
@@ -236,7 +273,11 @@ class ResNet(nn.Module):
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
-        if stride != 1 or self.inplanes != planes * block.expansion:
+        if (stride != 1 or self.inplanes != planes * block.expansion) and self.deep:
+            downsample = nn.Sequential(AvgPool2() if stride != 1 else nn.Identity(),
+                                       Conv2d(self.inplanes, planes * block.expansion, 1, 1),
+                                       BatchNorm2d(planes * block.expansion))
+        elif stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride),
                                        BatchNorm2d(planes * block.expansion))
         gw = dict(groups=self.groups, width_per_group=self.width_per_group, se=self.se)
@@ -251,6 +292,12 @@ class ResNet(nn.Module):
             for b in layer:
                 yield b
 
+    def stem(self):
+        """The stem's (conv, BatchNorm) pairs in forward order; each BatchNorm is followed by a ReLU."""
+        if not self.deep:
+            return [(self.conv1, self.bn1)]
+        return [(self.conv1[0], self.conv1[1]), (self.conv1[3], self.conv1[4]), (self.conv1[6], self.bn1)]
+
     def batchnorms(self) -> List[BatchNorm2d]:
         return [m for m in self.modules() if isinstance(m, BatchNorm2d)]
 
@@ -259,7 +306,8 @@ class ResNet(nn.Module):
 
     # ---------------------------------------------------------------- torch
     def forward_torch(self, x):
-        x = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
+        for conv, bn in self.stem():
+            x = F.relu(bn.forward_torch(conv.forward_torch(x)))
         x = F.max_pool2d(x, 3, 2, 1)
         for b in self.blocks():
             x = b.forward_torch(x)
@@ -317,16 +365,29 @@ def _se(fn: Callable[..., ResNet]) -> Callable[..., ResNet]:
     return lambda **kw: fn(se=True, **kw)
 
 
+def _d(fn: Callable[..., ResNet]) -> Callable[..., ResNet]:
+    return lambda **kw: fn(deep=True, **kw)
+
+
+def d_name(name: str) -> str:
+    """timm's name of the D variant: the ``d`` follows the depth (``resnet50d``, ``resnext50d_32x4d``)."""
+    head, sep, tail = name.partition("_")
+    return head + "d" + sep + tail
+
+
 ARCHS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101,
          "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d, "resnext101_32x8d": resnext101_32x8d,
          "resnext101_64x4d": resnext101_64x4d}
+_PLAIN_D = tuple(d_name(name) for name in ARCHS)
+ARCHS.update({d_name(name): _d(fn) for name, fn in list(ARCHS.items())})
 ARCHS.update({"se" + name: _se(fn) for name, fn in list(ARCHS.items())})
 # the grouped-bottleneck archs: bf16 HIP kernels (ops/conv.py gconv_*) or the torch backend, no fp32 HIP path
-GROUPED_ARCHS = ("resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d",
-                 "seresnext50_32x4d", "seresnext101_32x8d", "seresnext101_64x4d")
+GROUPED_ARCHS = tuple(a for a in ARCHS if "resnext" in a)
 # the squeeze-and-excitation archs: bf16 HIP kernels (ops/se.py) or the torch backend, no fp8 / fp32 HIP path
-SE_ARCHS = ("seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
-            "seresnext50_32x4d", "seresnext101_32x8d", "seresnext101_64x4d")
+SE_ARCHS = tuple(a for a in ARCHS if a.startswith("se"))
+# the ResNet-D archs (deep 3x3 stem, average-pool shortcut): bf16 HIP kernels (ops/conv.py nconv_*, ops/misc.py
+# avgpool2_*) or the torch backend, no fp8 / fp32 HIP path
+D_ARCHS = _PLAIN_D + tuple("se" + a for a in _PLAIN_D)
 
 
 def build(arch: str, num_classes: int = 1000, **kw) -> ResNet:

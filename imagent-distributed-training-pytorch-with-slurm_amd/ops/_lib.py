@@ -166,6 +166,11 @@ def _declare(name: str, lib) -> None:
             "imk_gconv_fwd": [vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp],
             "imk_gconv_dgrad": [vp, vp, vp] + [i32] * 8 + [vp],
             "imk_gconv_wgrad": [vp, vp, vp] + [i32] * 8 + [vp],
+            # narrow 3x3 convs of the ResNet-D stem (conv_narrow.hip), the 2x2 average pool of its shortcut (avgpool2.hip)
+            "imk_nconv_fwd": [vp] * 7 + [i32] * 9 + [vp],
+            "imk_nconv_wgrad": [vp] * 4 + [i32] * 7 + [vp],
+            "imk_avgpool2_fwd": [vp, vp, i32, i32, i32, i32, vp],
+            "imk_avgpool2_bwd": [vp, vp, i32, i32, i32, i32, vp],
             # squeeze-and-excitation block tail (se.hip)
             "imk_se_squeeze": [vp, vp, vp, i32, i32, i32, vp],
             "imk_se_bwd_reduce": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
@@ -261,6 +266,8 @@ def _declare(name: str, lib) -> None:
             f.restype = C.c_int
         lib.imk_bn_stats_det_floats.argtypes = [i64, i32]
         lib.imk_bn_stats_det_floats.restype = C.c_long
+        lib.imk_nconv_ws_floats.argtypes = [i32] * 6
+        lib.imk_nconv_ws_floats.restype = C.c_long
         lib.imk_se_reduce_floats.argtypes = [i32, i32, i32, i32]
         lib.imk_se_reduce_floats.restype = C.c_long
         lib.imk_se_excite_bwd_floats.argtypes = [i32, i32, i32]

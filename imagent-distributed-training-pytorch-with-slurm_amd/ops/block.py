@@ -36,6 +36,7 @@ from . import conv as _conv
 from .bn import bn_act_backward, bn_act_forward, bn_apply_backward, bn_scale_shift
 from .bn_gram import GramBN, gram_T, gram_coef, gram_dgrad, gram_fwd_stats, gram_wgrad
 from .conv import BNBwdFuse, conv_wgrad, gconv_dgrad, gconv_fwd, igemm_dgrad, igemm_fwd
+from .misc import avgpool2_bwd, avgpool2_fwd
 from .se import se_tail_backward, se_tail_forward
 
 
@@ -280,7 +281,7 @@ class BlockFn(torch.autograd.Function):
         x8 = q.lookup(x) if q is not None else None
         saved = [x]
         h, h8 = x, x8
-        ds = block.downsample
+        ds = block.shortcut()  # None, or the shortcut's (pool, conv, bn) (models/resnet.py Shortcut)
         # conv1's output as the previous block's conv3 launch left it (IMAGENT_NEXT_CONV1), valid only for the very
         # tensor it was computed from; after any other input, bn1's slab holds that launch's sums: cleared
         a1, stash = None, getattr(block, "_next1_in", None)
@@ -292,8 +293,11 @@ class BlockFn(torch.autograd.Function):
                 _lib.zero_(pairs[0][1].work.slab)
         # --fp8-wgrad: the e4m3 input copies (conv index / "ds" -> (bytes, exponent view)) kept for the backward pass
         wg8 = {}
-        if ds is not None and _keep8(q, ds[0], x8) is not None:
-            wg8["ds"] = _keep8(q, ds[0], x8)
+        if ds is not None and _keep8(q, ds.conv, x8) is not None:
+            wg8["ds"] = _keep8(q, ds.conv, x8)
+        # a D block's shortcut conv (1x1, stride 1) reads the 2x2 average of x; the pooled tensor is kept for that
+        # conv's weight gradient (1/4 of x, not recomputed)
+        xs = avgpool2_fwd(x) if (ds is not None and ds.pool is not None) else x
         # the downsample conv depends only on x: with IMAGENT_DS_SIDE=1 it runs on the (idle in forward) side stream
         # beside the main chain's memory-bound BN passes (off by default, see _DS_SIDE)
         side = streams.side_stream(x.device) if (ds is not None and x.is_cuda and _DS_SIDE) else None
@@ -301,7 +305,7 @@ class BlockFn(torch.autograd.Function):
         if side is not None:
             streams.wait(side, torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                ad = _fwd8(ds[0], x, x8, ds[1])
+                ad = _fwd8(ds.conv, xs, x8, ds.bn)
         xbn = [None] * len(pairs)  # xbn[i]: conv i applies the preceding BN + ReLU on its operand load
         gram = _gram_ok(block, q, x)  # bn3 backward in the Gram form: conv3's input must exist
         ss = None
@@ -351,8 +355,8 @@ class BlockFn(torch.autograd.Function):
                     streams.wait(cur, side)
                     ad.record_stream(cur)
                 else:
-                    ad = _fwd8(ds[0], x, x8, ds[1])
-                ssd = bn_scale_shift(ad, ds[1])
+                    ad = _fwd8(ds.conv, xs, x8, ds.bn)
+                ssd = bn_scale_shift(ad, ds.bn)
                 res, rsc = ad, ssd[0]
             aff, gram_P = gram_fwd_stats(bn, conv, h, h2sum, gws[1], add_shift=ssd[1] if ssd is not None else None,
                                          P=gws[4])
@@ -392,8 +396,8 @@ class BlockFn(torch.autograd.Function):
                     streams.wait(cur, side)
                     ad.record_stream(cur)
                 else:
-                    ad = _fwd8(ds[0], x, x8, ds[1])
-            idt = bn_act_forward(ad, None, ds[1], None, 0, False) if ds is not None else x
+                    ad = _fwd8(ds.conv, xs, x8, ds.bn)
+            idt = bn_act_forward(ad, None, ds.bn, None, 0, False) if ds is not None else x
             out, se_state = se_tail_forward(a, bn, idt, se)
             se_state = se_state[2:]
         elif ds is not None:
@@ -402,8 +406,8 @@ class BlockFn(torch.autograd.Function):
                 streams.wait(cur, side)
                 ad.record_stream(cur)  # allocated on the side stream, read / freed in main order
             else:
-                ad = _fwd8(ds[0], x, x8, ds[1])
-            out = bn_act_forward(a, ad, bn, ds[1], 2, True, q8=q8, ym=ym)
+                ad = _fwd8(ds.conv, xs, x8, ds.bn)
+            out = bn_act_forward(a, ad, bn, ds.bn, 2, True, q8=q8, ym=ym)
         else:
             ad = None
             out = bn_act_forward(a, x, bn, None, 1, True, q8=q8, ym=ym)
@@ -422,6 +426,7 @@ class BlockFn(torch.autograd.Function):
         block._T_done = False
         block._bnb_done = False
         ctx.block = block
+        ctx.xs = xs if xs is not x else None  # the pooled shortcut input of a D block
         ctx.xbn = xbn
         ctx.wg8 = wg8 or None
         ctx.gram = gram
@@ -451,7 +456,7 @@ class BlockFn(torch.autograd.Function):
         dout = dout.contiguous()
         H, W = x.shape[1], x.shape[2]
         conv_l, bn_l, _ = pairs[-1]
-        ds = block.downsample
+        ds = block.shortcut()  # None, or the shortcut's (pool, conv, bn) (models/resnet.py Shortcut)
         fuse = getattr(block, "_fuse_bnb", False)
         premasked = getattr(block, "_bnb_done", False)
         wg8 = ctx.wg8 or {}  # kept e4m3 input copies (--fp8-wgrad)
@@ -461,33 +466,40 @@ class BlockFn(torch.autograd.Function):
             if ctx.se_state is not None:
                 # the SE tail; its g is the gradient of the materialised shortcut bn_d(ad) (mode 0, no ReLU)
                 dA, g = se_tail_backward(dout, (a_last, out) + tuple(ctx.se_state), bn_l, block.se)
-                dAd, _ = bn_act_backward(g, ad, None, None, ds[1], None, 0, False)
+                dAd, _ = bn_act_backward(g, ad, None, None, ds.bn, None, 0, False)
                 dAd8 = None
             elif premasked and ctx.gram and fuse:
                 # bn3 in the Gram form (as for identity blocks below); the downsample BN alone gets an apply pass:
                 # its reductions (sum g, sum g xhat_d) sit in bn3's slab rows 1, 2 (read there, sgx_row=2)
                 T = _take_T(block, dout, outs[-1])
                 dA = gram_coef(bn_l, dout, T=T, w3=conv_l.w_bf16 if T is not None else None, hs=ctx.h2sum)
-                dAd, _ = bn_apply_backward(dout, ad, None, ds[1], None, 1, slab_of=bn_l, sgx_row=2)
+                dAd, _ = bn_apply_backward(dout, ad, None, ds.bn, None, 1, slab_of=bn_l, sgx_row=2)
                 dAd8 = None
             elif premasked:  # dout already masked + reduced by the next block's conv1 dgrad
                 g8a = q.grad_out(a_last, bn_l) if (q is not None and fp8_dgrad_ok(conv_l)) else None
-                g8b = q.grad_out(ad, ds[1]) if (q is not None and fp8_dgrad_ok(ds[0])) else None
-                dA, dAd = bn_apply_backward(dout, a_last, ad, bn_l, ds[1], 2, g8=(g8a, g8b))
+                g8b = q.grad_out(ad, ds.bn) if (q is not None and fp8_dgrad_ok(ds.conv)) else None
+                dA, dAd = bn_apply_backward(dout, a_last, ad, bn_l, ds.bn, 2, g8=(g8a, g8b))
                 dA8, dAd8 = _use8(q, g8a), _use8(q, g8b)
             else:
-                dA, dAd = bn_act_backward(dout, a_last, ad, out, bn_l, ds[1], 2, True)
+                dA, dAd = bn_act_backward(dout, a_last, ad, out, bn_l, ds.bn, 2, True)
                 dAd8 = None
-            dconv = ds[0]
+            dconv = ds.conv
             # a stride-2 1x1 downsample reaches only the even pixels: write those, no memset of the
             # rest (conv1's dgrad below accumulates with old_sub2 = zeros at the odd ones)
             sparse = dconv.stride == 2 and dconv.kh == 1 and dconv.kw == 1 and dconv.padding == 0
-            dX = igemm_dgrad(dAd, dconv.wt_bf16, (H, W), dconv.stride, dconv.padding, dconv.kh, dconv.kw,
-                             fp8=_dg8(dAd8, dconv), sparse=sparse)
+            if ds.pool is not None:
+                # a D block: the dense dgrad of the stride-1 shortcut conv on the pooled map, then the pool's
+                # backward writes every pixel of dX (no sub-pixel case); conv1's dgrad accumulates into it as ever
+                dXp = igemm_dgrad(dAd, dconv.wt_bf16, (ctx.xs.shape[1], ctx.xs.shape[2]), dconv.stride, dconv.padding,
+                                  dconv.kh, dconv.kw)
+                dX = avgpool2_bwd(dXp, (H, W))
+            else:
+                dX = igemm_dgrad(dAd, dconv.wt_bf16, (H, W), dconv.stride, dconv.padding, dconv.kh, dconv.kw,
+                                 fp8=_dg8(dAd8, dconv), sparse=sparse)
             if _wg8(dAd8, wg8.get("ds")) is not None:
                 conv_wgrad(dconv, dAd, x, fp8=_wg8(dAd8, wg8.get("ds")))
             else:
-                conv_wgrad(dconv, dAd, x)
+                conv_wgrad(dconv, dAd, x if ds.pool is None else ctx.xs)  # (a D block: the kept pooled input)
         elif ctx.se_state is not None:
             dA, dX = se_tail_backward(dout, (a_last, out) + tuple(ctx.se_state), bn_l, block.se)  # dX = masked dout
         elif premasked and ctx.gram and fuse:
@@ -550,12 +562,12 @@ class BlockFn(torch.autograd.Function):
                 if fuse and prev is not None and prev._last_bn is not None:
                     pa, pad_, pym = prev._last_bn
                     pbn = prev.convs_bns()[-1][1]
-                    pds = prev.downsample
+                    pds = prev.shortcut()
                     # the previous block's bn3 backward takes the Gram form: sum(g xhat3) from g^T h2, x3 not read
                     nox = _GRAM_NOX and getattr(prev, "_gram", False) and pym is not None
                     gt = _gram_t_target(prev, conv, nox, _dg8(dA8, conv), pad_)
                     fz = BNBwdFuse(None if nox else pa, pbn, y=pym, x2=pad_,
-                                   bn2=pds[1] if pds is not None else None, gramt=gt)
+                                   bn2=pds.bn if pds is not None else None, gramt=gt)
                 if g_read is not None:
                     torch.cuda.current_stream().wait_event(g_read)
                 igemm_dgrad(dA, conv.wt_bf16, (H, W), conv.stride, conv.padding, conv.kh, conv.kw, out=dX,

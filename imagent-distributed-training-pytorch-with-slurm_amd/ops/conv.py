@@ -529,6 +529,95 @@ def _gconv_mod_check(mod) -> None:
         raise RuntimeError(f"grouped conv: only 3x3, pad 1, equal widths have a kernel (got {mod.extra_repr()})")
 
 
+# --------------------------------------------------------------------------
+# narrow 3x3 convs (the ResNet-D deep stem; conv_narrow.hip)
+# --------------------------------------------------------------------------
+
+def narrow_shape(ci: int, co: int, stride: int) -> bool:
+    """The convs of the deep stem: the 4 (3 real) -> 32 stride-2 conv on the image, 32 -> 32 and 32 -> 64 stride 1."""
+    return (ci in (3, 4) and co == 32 and stride == 2) or (ci == 32 and co in (32, 64) and stride == 1)
+
+
+def _narrow(mod) -> bool:
+    ci = getattr(mod, "in_channels", None)  # (a stand-in module without channel counts: not one of the stem's)
+    return (ci is not None and mod.kh == 3 and mod.kw == 3 and mod.padding == 1 and getattr(mod, "groups", 1) == 1
+            and narrow_shape(ci, mod.out_channels, mod.stride))
+
+
+def _narrow_act(mod) -> bool:
+    """Forward and dgrad on the narrow kernels: the image conv and 32 -> 32. The 32 -> 64 conv keeps the dense route
+    for both (measured faster there at 256 x 112^2: 446 vs 667 us forward, 521 vs 567 us dgrad, profiles/resnet_d.md);
+    its weight gradient, like the other two, has no dense alternative and takes the narrow kernel."""
+    return _narrow(mod) and mod.out_channels == 32
+
+
+def _nconv_rc(rc: int, what: str, ci: int, co: int, stride: int) -> None:
+    if rc == -106:
+        raise RuntimeError(f"{what}: no narrow kernel for {ci} -> {co} channels, stride {stride} (4 -> 32 stride 2, "
+                           f"32 -> 32 / 64 stride 1 and the 64 -> 32 dgrad) failed with code {rc}")
+    _lib.check(rc, what)
+
+
+def _nconv_ws(N: int, OH: int, OW: int, ci: int, co: int, wgrad: bool, device) -> torch.Tensor:
+    n = _lib.kernels().imk_nconv_ws_floats(N, OH, OW, ci, co, 1 if wgrad else 0)
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def _nconv_launch(x, w, stride, mirror, stats, affine, relu, what):
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and w.dtype == torch.bfloat16 and w.is_contiguous()
+    N, H, W, Ci = x.shape
+    Co, cw = w.shape[0], w.shape[3]
+    assert w.dim() == 4 and tuple(w.shape[1:3]) == (3, 3), tuple(w.shape)
+    OH, OW = conv_out_size(H, 3, stride, 1), conv_out_size(W, 3, stride, 1)
+    out = torch.empty((N, OH, OW, Co), device=x.device, dtype=torch.bfloat16)
+    shift, ws = None, None
+    if stats is not None:
+        if hasattr(stats, "slab"):  # a BatchNorm's workspace: shifted sums around its last batch mean
+            shift = stats.save if _SHIFT else None
+            stats = stats.slab
+        ws = _nconv_ws(N, OH, OW, Ci, Co, False, x.device)
+    if affine is not None:
+        assert affine.shape == (2, Co) and affine.dtype == torch.float32 and affine.is_contiguous()
+    _nconv_rc(_lib.kernels().imk_nconv_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), _lib.ptr(affine),
+                                           _lib.ptr(stats), _lib.ptr(shift), _lib.ptr(ws), N, H, W, Ci, Co, cw, stride,
+                                           1 if mirror else 0, 1 if relu else 0, _lib.stream_ptr()),
+              what, Ci, Co, stride)
+    return out
+
+
+def nconv_fwd(x: torch.Tensor, w: torch.Tensor, stride: int, stats=None, affine: Optional[torch.Tensor] = None,
+              relu: bool = False) -> torch.Tensor:
+    """y[N,OH,OW,Co] = 3x3 conv, pad 1, of x[N,H,W,Ci] with ``w`` ``[Co,3,3,Ci]`` bf16 on the narrow kernels
+    (:func:`narrow_shape`). The image conv reads x with 4 channels and ``w`` with 3 or 4 (``[Co,3,3,3]``: the plain
+    shadow of a 3-channel parameter). ``stats`` / ``affine`` / ``relu`` as :func:`igemm_fwd`; the BatchNorm sums take
+    no float atomics (per-block partials folded in fixed order), so the deterministic mode reads them too."""
+    return _nconv_launch(x, w, stride, False, stats, affine, relu, "narrow conv fwd")
+
+
+def nconv_dgrad(dy: torch.Tensor, wt: torch.Tensor) -> torch.Tensor:
+    """dx[N,H,W,Ci] = dgrad of the stride-1 :func:`nconv_fwd` (32 -> 32, 32 -> 64): the forward kernel on the
+    transposed shadow ``wt`` ``[Ci,3,3,Co]`` with mirrored taps."""
+    return _nconv_launch(dy, wt, 1, True, None, None, False, "narrow conv dgrad")
+
+
+def nconv_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, stride: int) -> None:
+    """dw (fp32, ``[Co][3][3][cw]`` in memory, cw = Ci or, for the 4-channel image, 3 / 4) += wgrad(dy, x): per-block
+    fp32 partials, then one fold in fixed order (no float atomics: bitwise repeatable)."""
+    N, H, W, Ci = x.shape
+    Co = dy.shape[3]
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and x.dtype == torch.bfloat16 and x.is_contiguous()
+    assert dw.dtype == torch.float32 and dw.numel() % (Co * 9) == 0 and dy.shape[0] == N
+    assert (dy.shape[1], dy.shape[2]) == (conv_out_size(H, 3, stride, 1), conv_out_size(W, 3, stride, 1)), dy.shape
+    cw = dw.numel() // (Co * 9)
+    if dw.dim() == 4 and tuple(dw.shape) == (Co, cw, 3, 3):
+        assert dw.permute(0, 2, 3, 1).is_contiguous(), "narrow conv wgrad: channels-last gradient storage"
+    else:
+        assert dw.is_contiguous()
+    ws = _nconv_ws(N, dy.shape[1], dy.shape[2], Ci, Co, True, x.device)
+    _nconv_rc(_lib.kernels().imk_nconv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), N, H, W, Ci,
+                                             Co, cw, stride, _lib.stream_ptr()), "narrow conv wgrad", Ci, Co, stride)
+
+
 def colsum_into(x2d: torch.Tensor, out: torch.Tensor) -> None:
     R, Cc = x2d.shape
     _lib.check(_lib.kernels().imk_colsum_bf16(x2d.data_ptr(), out.data_ptr(), R, Cc, _lib.stream_ptr()),
@@ -550,6 +639,8 @@ class ConvFn(torch.autograd.Function):
         if _grouped(mod):
             _gconv_mod_check(mod)
             y = gconv_fwd(x, mod.w_bf16, mod.stride, mod.groups, stats=stats)
+        elif _narrow_act(mod):
+            y = nconv_fwd(x, mod.w_bf16, mod.stride, stats=stats)
         else:
             y = igemm_fwd(x, mod.w_bf16, mod.stride, mod.padding, mod.kh, mod.kw, stats=stats,
                           stem=getattr(mod, "stem", False))
@@ -566,6 +657,8 @@ class ConvFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0] and _grouped(mod):
             dx = gconv_dgrad(dy, mod.wt_bf16, (x.shape[1], x.shape[2]), mod.stride, mod.groups)
+        elif ctx.needs_input_grad[0] and _narrow_act(mod):
+            dx = nconv_dgrad(dy, mod.wt_bf16)
         elif ctx.needs_input_grad[0]:
             dx = igemm_dgrad(dy, mod.wt_bf16, (x.shape[1], x.shape[2]), mod.stride, mod.padding, mod.kh,
                              mod.kw)
@@ -600,6 +693,11 @@ def _conv_wgrad(mod, dy: torch.Tensor, x: torch.Tensor, xbn: Optional[torch.Tens
     if _grouped(mod):  # (bf16 only: no fp8 copies, no operand-path BatchNorm)
         assert xbn is None and fp8 is None, "grouped conv wgrad: bf16 operands only"
         gconv_wgrad(dy, x, mod.weight.grad, mod.stride, mod.groups)
+        notify_ready(mod.weight)
+        return
+    if _narrow(mod):  # (bf16 only, as above)
+        assert xbn is None and fp8 is None, "narrow conv wgrad: bf16 operands only"
+        nconv_wgrad(dy, x, mod.weight.grad, mod.stride)
         notify_ready(mod.weight)
         return
     gp = getattr(mod, "grad_pad", None)

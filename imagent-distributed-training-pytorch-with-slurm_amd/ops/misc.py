@@ -200,6 +200,43 @@ class AvgPoolFn(torch.autograd.Function):
         return dx
 
 
+def avgpool2_fwd(x: torch.Tensor) -> torch.Tensor:
+    """``AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False)`` on NHWC bf16 [N,H,W,C] (C % 8 == 0): the
+    ResNet-D shortcut's pool; the last window of an odd map averages the 2 or 1 pixels it holds."""
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4
+    N, H, W, Cc = x.shape
+    y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, Cc), device=x.device, dtype=torch.bfloat16)
+    _lib.check(_lib.kernels().imk_avgpool2_fwd(x.data_ptr(), y.data_ptr(), N, H, W, Cc, _lib.stream_ptr()),
+               "avgpool2")
+    return y
+
+
+def avgpool2_bwd(dy: torch.Tensor, in_hw) -> torch.Tensor:
+    """dx[N,H,W,C] of :func:`avgpool2_fwd`: every pixel gets its window's dy divided by the window's pixel count
+    (a dense write of all of dx)."""
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and dy.dim() == 4
+    N, OH, OW, Cc = dy.shape
+    H, W = in_hw
+    assert OH == (H + 1) // 2 and OW == (W + 1) // 2, (tuple(dy.shape), in_hw)
+    dx = torch.empty((N, H, W, Cc), device=dy.device, dtype=torch.bfloat16)
+    _lib.check(_lib.kernels().imk_avgpool2_bwd(dy.data_ptr(), dx.data_ptr(), N, H, W, Cc, _lib.stream_ptr()),
+               "avgpool2 bwd")
+    return dx
+
+
+class AvgPool2Fn(torch.autograd.Function):
+    """:func:`avgpool2_fwd` as an autograd node (the per-op path; ops/block.py schedules the pair itself)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (x.shape[1], x.shape[2])
+        return avgpool2_fwd(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return avgpool2_bwd(dy.contiguous(), ctx.hw)
+
+
 # ------------------------------------------------------------ loss+metrics
 class XentFn(torch.autograd.Function):
     """Mean softmax cross-entropy (nn.CrossEntropyLoss, imagenet.py:323) with
