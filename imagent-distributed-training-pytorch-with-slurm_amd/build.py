@@ -82,11 +82,11 @@ def _run(cmd: List[str]) -> None:
 
 
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
-# per-file additions: the grouped convs, the squeeze-excite tail, the narrow stem convs and the 2x2 average pool are
-# compiled without the packed fp32 VALU forms (v_pk_*_f32)
+# per-file additions: the grouped convs, the squeeze-excite tail, the narrow stem convs, the 2x2 average pool and the
+# blur pool are compiled without the packed fp32 VALU forms (v_pk_*_f32)
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"conv_group.hip": NO_PK_F32, "se.hip": NO_PK_F32, "conv_narrow.hip": NO_PK_F32,
-              "avgpool2.hip": NO_PK_F32}
+              "avgpool2.hip": NO_PK_F32, "blurpool.hip": NO_PK_F32}
 
 
 def _file_flags(src: str) -> List[str]:

@@ -20,6 +20,26 @@ import argparse
 import sys
 
 
+_ARCHS = [
+    "resnet18", "resnet34", "resnet50", "resnet101", "resnet152", "resnext50_32x4d", "resnext101_32x8d",
+    "resnext101_64x4d", "seresnet18", "seresnet34", "seresnet50", "seresnet101", "seresnet152",
+    "seresnext50_32x4d", "seresnext101_32x8d", "seresnext101_64x4d", "resnet18d", "resnet34d",
+    "resnet50d", "resnet101d", "resnet152d", "resnext50d_32x4d", "resnext101d_32x8d",
+    "resnext101d_64x4d", "seresnet18d", "seresnet34d", "seresnet50d", "seresnet101d", "seresnet152d",
+    "seresnext50d_32x4d", "seresnext101d_32x8d", "seresnext101d_64x4d"]
+
+
+def _aa_archs(archs):
+    """The anti-aliased twins of ``archs`` (models/resnet.py AA_ARCHS, composed here without importing torch):
+    ``blur`` / ``aa`` after the ``resnet`` / ``resnext`` head."""
+    out = []
+    for name in archs:
+        se, rest = ("se", name[2:]) if name.startswith("se") else ("", name)
+        head = "resnext" if rest.startswith("resnext") else "resnet"
+        out += [se + head + tag + rest[len(head):] for tag in ("blur", "aa")]
+    return out
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Imagenet Pytorch (MI355X-native)")
     # --- reference flags (same names, same defaults) ---
@@ -30,23 +50,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lr", type=float, default=0.1, metavar="LR")
     p.add_argument("--save-model", action="store_true", default=False, help="save the best model")
     # --- model / data ---
-    p.add_argument("--arch", default="resnet18", choices=["resnet18", "resnet34", "resnet50", "resnet101",
-                                                           "resnet152", "resnext50_32x4d", "resnext101_32x8d",
-                                                           "resnext101_64x4d", "seresnet18", "seresnet34",
-                                                           "seresnet50", "seresnet101", "seresnet152",
-                                                           "seresnext50_32x4d", "seresnext101_32x8d",
-                                                           "seresnext101_64x4d", "resnet18d", "resnet34d", "resnet50d",
-                                                           "resnet101d", "resnet152d", "resnext50d_32x4d",
-                                                           "resnext101d_32x8d", "resnext101d_64x4d", "seresnet18d",
-                                                           "seresnet34d", "seresnet50d", "seresnet101d", "seresnet152d",
-                                                           "seresnext50d_32x4d", "seresnext101d_32x8d",
-                                                           "seresnext101d_64x4d"],
+    p.add_argument("--arch", default="resnet18", choices=_ARCHS + _aa_archs(_ARCHS),
                    help="resnext*: grouped bottlenecks (conv2 on the grouped HIP kernels, bf16; --dtype fp8 keeps "
                         "those convs bf16; not with --dtype fp32 on the HIP kernels). se*: a squeeze-and-excitation "
                         "gate at the end of each block (block tail on the HIP kernels of ops/se.py; --dtype bf16 "
                         "only on the HIP kernels). *d (resnet50d, resnext50d_32x4d, ..): ResNet-D, a deep 3x3 stem and an "
                         "average-pool shortcut (ops/conv.py nconv_*, ops/misc.py avgpool2_*; --dtype bf16 only on the HIP "
-                        "kernels)")
+                        "kernels). resnetblur* / resnetaa* (resnetblur50, resnetaa50d, seresnextaa101d_32x8d, ..): "
+                        "anti-aliased, a BlurPool / 2x2 average pool at every stride-2 point (ops/misc.py blurpool_*; "
+                        "--dtype bf16 only on the HIP kernels)")
     p.add_argument("--image-size", type=int, default=448)
     p.add_argument("--deterministic", action="store_true",
                    help="BatchNorm statistics without float atomics (fixed-order reduction passes): two runs "

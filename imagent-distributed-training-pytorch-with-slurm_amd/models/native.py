@@ -25,7 +25,7 @@ from ..ops.block import BlockFn
 from ..ops.bn import BNActFn, bn_eval, running_update
 from ..ops.conv import ConvFn, LinearFn, _narrow_act, conv_out_size, deterministic, gconv_fwd, igemm_fwd, nconv_fwd
 from ..ops.se import SETailFn, se_gate_eval
-from ..ops.misc import AvgPool2Fn, AvgPoolFn, BNReluPoolFn, avgpool2_fwd, MaxPoolFn, StemFn, TransposePlan, maxpool_eval, stem_fused_ok
+from ..ops.misc import AvgPool2Fn, AvgPoolFn, BlurPoolFn, BNReluPoolFn, avgpool2_fwd, blurpool_fwd, MaxPoolFn, StemFn, TransposePlan, maxpool_eval, stem_fused_ok
 from .arena import ParamArena
 from .resnet import BasicBlock, BatchNorm2d, BNWork, Bottleneck, Conv2d, Linear, ResNet
 
@@ -44,6 +44,8 @@ class NativeState:
             raise ValueError("the squeeze-and-excitation archs run bf16 on the HIP kernels: no fp8 path")
         if fp8 and getattr(model, "deep", False):
             raise ValueError("the ResNet-D archs run bf16 on the HIP kernels: no fp8 path")
+        if fp8 and getattr(model, "aa", None) is not None:
+            raise ValueError("the anti-aliased archs run bf16 on the HIP kernels: no fp8 path")
         named = list(model.named_parameters())
         self.arena = ParamArena(named, self.device, order=order, with_shadow=True)
         self.model = model
@@ -373,6 +375,13 @@ def _conv(x, conv: Conv2d, bn: Optional[BatchNorm2d], train: bool):
 _FUSED_STEM = True
 
 
+def _aa_pool(x, pool, train):
+    """An anti-aliased downsampling point on the per-op / eval paths: the plain BlurPool or the 2x2 average pool."""
+    if pool.kind == "blur":
+        return BlurPoolFn.apply(x) if train else blurpool_fwd(x)
+    return AvgPool2Fn.apply(x) if train else avgpool2_fwd(x)
+
+
 def _bn(x, bn, relu, train, x2=None, bn2=None, mode=0):
     if train:
         return BNActFn.apply(x, x2, bn, bn2, mode, relu)
@@ -400,7 +409,16 @@ def forward_hip(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         rows.append(x.numel() // x.shape[-1])
         x = _bn(x, bn, True, train)
     c_last = stem[-1][0]
-    if model.deep and _FUSED_STEM and not deterministic():  # BN + ReLU inside the max-pool, as below
+    if model.aa is not None:
+        # anti-aliased: the fused BN + ReLU + max-pool nodes are 3 / 2 / 1 pools, so BN + ReLU is a node of its own;
+        # then max-pool(3, 1, 1) -> BlurPool ("blur"), or the 2x2 average pool in the max-pool's place ("avg")
+        y = _conv(x, c_last, model.bn1, train)
+        rows.append(y.numel() // y.shape[-1])
+        y = _bn(y, model.bn1, True, train)
+        if model.aa == "blur":
+            y = MaxPoolFn.apply(y, 3, 1, 1)
+        y = _aa_pool(y, model.stem_pool, train)
+    elif model.deep and _FUSED_STEM and not deterministic():  # BN + ReLU inside the max-pool, as below
         y = _conv(x, c_last, model.bn1, train)
         rows.append(y.numel() // y.shape[-1])
         y = BNReluPoolFn.apply(y, model.bn1, 3, 2, 1)
@@ -439,10 +457,13 @@ def forward_hip(model: ResNet, x: torch.Tensor) -> torch.Tensor:
         idt = y
         pairs = b.convs_bns()
         out = y
-        for conv, bn, relu in pairs[:-1]:
+        pl = b.pool()  # an anti-aliased block: (pool, index of the pair it follows)
+        for i, (conv, bn, relu) in enumerate(pairs[:-1]):
             a = _conv(out, conv, bn, train)
             rows.append(a.numel() // a.shape[-1])
             out = _bn(a, bn, True, train)
+            if pl is not None and pl[1] == i:
+                out = _aa_pool(out, pl[0], train)
         conv, bn, _ = pairs[-1]
         a = _conv(out, conv, bn, train)
         rows.append(a.numel() // a.shape[-1])
@@ -508,12 +529,18 @@ def _forward_eval(model: ResNet, x: torch.Tensor) -> torch.Tensor:
     y = x
     for c, bn in model.stem():
         y = conv(y, c, bn, True)
-    y = maxpool_eval(y, 3, 2, 1)
+    if model.aa is not None:  # max-pool(3, 1, 1) -> BlurPool, or the average pool alone
+        y = _aa_pool(maxpool_eval(y, 3, 1, 1) if model.aa == "blur" else y, model.stem_pool, False)
+    else:
+        y = maxpool_eval(y, 3, 2, 1)
     for b in model.blocks():
         pairs = b.convs_bns()
         h = y
-        for c, bn, _ in pairs[:-1]:
+        pl = b.pool()  # an anti-aliased block: the plain pool after that pair's folded affine + ReLU conv
+        for i, (c, bn, _) in enumerate(pairs[:-1]):
             h = conv(h, c, bn, True)
+            if pl is not None and pl[1] == i:
+                h = _aa_pool(h, pl[0], False)
         c, bn, _ = pairs[-1]
         # the block's last conv accumulates onto the shortcut: the downsample conv's output, or the block
         # input itself, in place (no later reader: every consumer of y in this block has run)

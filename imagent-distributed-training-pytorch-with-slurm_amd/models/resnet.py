@@ -3,7 +3,9 @@ and their squeeze-and-excitation variants (``seresnet*`` / ``seresnext*``: a cha
 last BatchNorm, parameter names ``layerL.i.se.fc1.weight`` .. as in timm), and the ResNet-D variants of all of them
 (``resnet50d``, ``resnext50d_32x4d``, ``seresnet50d`` ..: timm's ``stem_type='deep', stem_width=32, avg_down=True`` --
 ``conv1`` is a Sequential of three 3x3 convs, a downsampling shortcut is pool -> 1x1 stride-1 conv -> BN under
-``downsample.0/.1/.2``).
+``downsample.0/.1/.2``), and the anti-aliased variants of all of those (``resnetblur50``, ``resnetaa50d``,
+``seresnextaa101d_32x8d`` ..: timm's ``aa_layer`` -- the conv that carried a block's stride runs at stride 1 and a
+parameter-free pool halves the map after its BatchNorm + ReLU; same keys, shapes and counts as the base arch).
 
 The reference instantiates ``torchvision.models.resnet18(pretrained=False,
 num_classes=1000)`` (``/root/reference/imagenet.py:312``); torchvision is not
@@ -133,10 +135,32 @@ class SEModule(nn.Module):
 
 
 class AvgPool2(nn.Module):
-    """The ResNet-D shortcut's pool: ``AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False)``; no parameters."""
+    """The ResNet-D shortcut's pool: ``AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False)``; no parameters. Also
+    the pool of the ``aa`` archs' stride-2 points (timm ``aa_layer=nn.AvgPool2d``; equal to it on even maps)."""
+
+    kind = "avg"
 
     def forward_torch(self, x):
         return F.avg_pool2d(x, 2, 2, ceil_mode=True, count_include_pad=False)
+
+
+class BlurPool2(nn.Module):
+    """The anti-aliased archs' BlurPool (timm ``BlurPool2d(filt_size=3, stride=2)``): depthwise [1,2,1]^T [1,2,1] / 16
+    at stride 2 over the reflect-padded map. No parameters and no buffer (timm's filter is a non-persistent one): no
+    state-dict key, nothing for the weight average or the buffer broadcast to carry."""
+
+    kind = "blur"
+
+    def forward_torch(self, x):
+        from ..ops.misc import blurpool_torch
+        return blurpool_torch(x)
+
+
+def _aa_pool(aa: Optional[str]) -> Optional[nn.Module]:
+    """The pool of an anti-aliased downsampling point: ``"blur"`` BlurPool, ``"avg"`` the 2x2 average pool."""
+    if aa not in (None, "blur", "avg"):
+        raise ValueError(f"aa must be None, 'blur' or 'avg', got {aa!r}")
+    return None if aa is None else (BlurPool2() if aa == "blur" else AvgPool2())
 
 
 class Shortcut:
@@ -174,11 +198,15 @@ class BNWork:
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64, se=False):
+    aa_after = 0  # an anti-aliased block's pool follows the (conv1, bn1) pair
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64, se=False, aa=None):
         super().__init__()
         if groups != 1 or width_per_group != 64:
             raise ValueError("BasicBlock only supports groups=1 and width_per_group=64")
-        self.conv1 = Conv2d(inplanes, planes, 3, stride, 1)
+        # anti-aliased (stride-2 blocks only): conv1 at stride 1, the pool after bn1 + ReLU
+        self.aa = _aa_pool(aa) if stride == 2 else None
+        self.conv1 = Conv2d(inplanes, planes, 3, 1 if self.aa is not None else stride, 1)
         self.bn1 = BatchNorm2d(planes)
         self.conv2 = Conv2d(planes, planes, 3, 1, 1)
         self.bn2 = BatchNorm2d(planes)
@@ -192,8 +220,14 @@ class BasicBlock(nn.Module):
     def shortcut(self) -> Optional["Shortcut"]:
         return None if self.downsample is None else Shortcut(self.downsample)
 
+    def pool(self):
+        """(pool module, index of the (conv, bn) pair whose ReLU it follows) of an anti-aliased block, else None."""
+        return None if self.aa is None else (self.aa, self.aa_after)
+
     def forward_torch(self, x):
         out = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
+        if self.aa is not None:
+            out = self.aa.forward_torch(out)
         out = self.bn2.forward_torch(self.conv2.forward_torch(out))
         if self.se is not None:
             out = self.se.forward_torch(out)
@@ -204,12 +238,16 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64, se=False):
+    aa_after = 1  # an anti-aliased block's pool follows the (conv2, bn2) pair
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, width_per_group=64, se=False, aa=None):
         super().__init__()
         width = int(planes * width_per_group / 64) * groups  # torchvision's rule (ResNeXt: groups > 1)
         self.conv1 = Conv2d(inplanes, width, 1)
         self.bn1 = BatchNorm2d(width)
-        self.conv2 = Conv2d(width, width, 3, stride, 1, groups=groups)
+        # anti-aliased (stride-2 blocks only): conv2 at stride 1, the pool after bn2 + ReLU
+        self.aa = _aa_pool(aa) if stride == 2 else None
+        self.conv2 = Conv2d(width, width, 3, 1 if self.aa is not None else stride, 1, groups=groups)
         self.bn2 = BatchNorm2d(width)
         self.conv3 = Conv2d(width, planes * 4, 1)
         self.bn3 = BatchNorm2d(planes * 4)
@@ -223,9 +261,15 @@ class Bottleneck(nn.Module):
     def shortcut(self) -> Optional["Shortcut"]:
         return None if self.downsample is None else Shortcut(self.downsample)
 
+    def pool(self):
+        """(pool module, index of the (conv, bn) pair whose ReLU it follows) of an anti-aliased block, else None."""
+        return None if self.aa is None else (self.aa, self.aa_after)
+
     def forward_torch(self, x):
         out = F.relu(self.bn1.forward_torch(self.conv1.forward_torch(x)))
         out = F.relu(self.bn2.forward_torch(self.conv2.forward_torch(out)))
+        if self.aa is not None:
+            out = self.aa.forward_torch(out)
         out = self.bn3.forward_torch(self.conv3.forward_torch(out))
         if self.se is not None:
             out = self.se.forward_torch(out)
@@ -244,9 +288,13 @@ class ResNet(nn.Module):
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: List[int],
                  num_classes: int = 1000, zero_init_residual: bool = False, groups: int = 1,
-                 width_per_group: int = 64, se: bool = False, deep: bool = False):
+                 width_per_group: int = 64, se: bool = False, deep: bool = False, aa: Optional[str] = None):
         super().__init__()
         self.block = block
+        # anti-aliased (timm aa_layer): "blur" BlurPool / "avg" the 2x2 average pool at every stride-2 point; the
+        # stem's max-pool becomes max-pool(3, 1, 1) -> BlurPool, or the average pool alone
+        self.aa = aa
+        self.stem_pool = _aa_pool(aa)
         self.groups, self.width_per_group, self.se = groups, width_per_group, se
         # ResNet-D (timm stem_type='deep', stem_width=32, avg_down=True): three 3x3 stem convs, pooled shortcuts
         self.deep = deep
@@ -281,7 +329,7 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(Conv2d(self.inplanes, planes * block.expansion, 1, stride),
                                        BatchNorm2d(planes * block.expansion))
         gw = dict(groups=self.groups, width_per_group=self.width_per_group, se=self.se)
-        layers = [block(self.inplanes, planes, stride, downsample, **gw)]
+        layers = [block(self.inplanes, planes, stride, downsample, aa=self.aa, **gw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
             layers.append(block(self.inplanes, planes, **gw))
@@ -308,7 +356,12 @@ class ResNet(nn.Module):
     def forward_torch(self, x):
         for conv, bn in self.stem():
             x = F.relu(bn.forward_torch(conv.forward_torch(x)))
-        x = F.max_pool2d(x, 3, 2, 1)
+        if self.aa == "blur":
+            x = self.stem_pool.forward_torch(F.max_pool2d(x, 3, 1, 1))
+        elif self.aa == "avg":
+            x = self.stem_pool.forward_torch(x)
+        else:
+            x = F.max_pool2d(x, 3, 2, 1)
         for b in self.blocks():
             x = b.forward_torch(x)
         x = torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
@@ -375,11 +428,27 @@ def d_name(name: str) -> str:
     return head + "d" + sep + tail
 
 
+def _aa(fn: Callable[..., ResNet], kind: str) -> Callable[..., ResNet]:
+    return lambda **kw: fn(aa=kind, **kw)
+
+
+def aa_name(name: str, tag: str) -> str:
+    """timm's name of an anti-aliased variant: ``blur`` / ``aa`` follows the ``resnet`` / ``resnext`` head
+    (``resnetblur50``, ``resnetaa50d``, ``resnextblur50_32x4d``)."""
+    head = "resnext" if name.startswith("resnext") else "resnet"
+    if not name.startswith(head):
+        raise ValueError(f"aa_name: {name!r} does not start with resnet / resnext")
+    return head + tag + name[len(head):]
+
+
 ARCHS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "resnet101": resnet101,
          "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d, "resnext101_32x8d": resnext101_32x8d,
          "resnext101_64x4d": resnext101_64x4d}
 _PLAIN_D = tuple(d_name(name) for name in ARCHS)
 ARCHS.update({d_name(name): _d(fn) for name, fn in list(ARCHS.items())})
+_PLAIN_AA = tuple(aa_name(name, tag) for name in ARCHS for tag in ("blur", "aa"))
+ARCHS.update({aa_name(name, tag): _aa(fn, kind) for name, fn in list(ARCHS.items())
+              for tag, kind in (("blur", "blur"), ("aa", "avg"))})
 ARCHS.update({"se" + name: _se(fn) for name, fn in list(ARCHS.items())})
 # the grouped-bottleneck archs: bf16 HIP kernels (ops/conv.py gconv_*) or the torch backend, no fp32 HIP path
 GROUPED_ARCHS = tuple(a for a in ARCHS if "resnext" in a)
@@ -388,6 +457,9 @@ SE_ARCHS = tuple(a for a in ARCHS if a.startswith("se"))
 # the ResNet-D archs (deep 3x3 stem, average-pool shortcut): bf16 HIP kernels (ops/conv.py nconv_*, ops/misc.py
 # avgpool2_*) or the torch backend, no fp8 / fp32 HIP path
 D_ARCHS = _PLAIN_D + tuple("se" + a for a in _PLAIN_D)
+# the anti-aliased archs (BlurPool / average pool at the stride-2 points): bf16 HIP kernels (ops/misc.py blurpool_*,
+# avgpool2_*) or the torch backend, no fp8 / fp32 HIP path
+AA_ARCHS = _PLAIN_AA + tuple("se" + a for a in _PLAIN_AA)
 
 
 def build(arch: str, num_classes: int = 1000, **kw) -> ResNet:

@@ -171,6 +171,9 @@ def _declare(name: str, lib) -> None:
             "imk_nconv_wgrad": [vp] * 4 + [i32] * 7 + [vp],
             "imk_avgpool2_fwd": [vp, vp, i32, i32, i32, i32, vp],
             "imk_avgpool2_bwd": [vp, vp, i32, i32, i32, i32, vp],
+            # the anti-aliased archs' blur pool (blurpool.hip): x, ss | NULL, y / dy, dx
+            "imk_blurpool_fwd": [vp, vp, vp, i32, i32, i32, i32, vp],
+            "imk_blurpool_bwd": [vp, vp, i32, i32, i32, i32, vp],
             # squeeze-and-excitation block tail (se.hip)
             "imk_se_squeeze": [vp, vp, vp, i32, i32, i32, vp],
             "imk_se_bwd_reduce": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],

@@ -36,7 +36,7 @@ from . import conv as _conv
 from .bn import bn_act_backward, bn_act_forward, bn_apply_backward, bn_scale_shift
 from .bn_gram import GramBN, gram_T, gram_coef, gram_dgrad, gram_fwd_stats, gram_wgrad
 from .conv import BNBwdFuse, conv_wgrad, gconv_dgrad, gconv_fwd, igemm_dgrad, igemm_fwd
-from .misc import avgpool2_bwd, avgpool2_fwd
+from .misc import avgpool2_bwd, avgpool2_fwd, blurpool_bwd, blurpool_fwd
 from .se import se_tail_backward, se_tail_forward
 
 
@@ -307,7 +307,13 @@ class BlockFn(torch.autograd.Function):
             with torch.cuda.stream(side):
                 ad = _fwd8(ds.conv, xs, x8, ds.bn)
         xbn = [None] * len(pairs)  # xbn[i]: conv i applies the preceding BN + ReLU on its operand load
-        gram = _gram_ok(block, q, x)  # bn3 backward in the Gram form: conv3's input must exist
+        # an anti-aliased stride-2 block: (pool, i) -- the pool halves the map after pair i's BatchNorm + ReLU. The conv
+        # after it reads (and its dgrad writes) the pooled resolution, so nothing that takes the dgrad output for the
+        # BatchNorm input's gradient or needs the normalised tensor applies to that block: no Gram-form bn3 (and with
+        # it no fused3 / next1 / gram_T), no operand-path BatchNorm and no fused BN-backward epilogue for that conv
+        pl = block.pool()
+        blur = pl is not None and pl[0].kind == "blur"  # (else "avg": the 2x2 average pool)
+        gram = pl is None and _gram_ok(block, q, x)  # bn3 backward in the Gram form: conv3's input must exist
         ss = None
         h2sum = None  # Gram form: colsum(h2), accumulated by the BN pass that writes h2
         for i, (conv, bn, _) in enumerate(pairs[:-1]):
@@ -319,6 +325,14 @@ class BlockFn(torch.autograd.Function):
             if ss is None and _keep8(q, conv, h8) is not None:
                 wg8[i] = _keep8(q, conv, h8)
             ss = None
+            if pl is not None and pl[1] == i:
+                if blur:  # BatchNorm + ReLU + BlurPool in one pass from the raw conv output (blurpool.hip)
+                    h = blurpool_fwd(a, bn_scale_shift(a, bn))
+                else:
+                    h = avgpool2_fwd(bn_act_forward(a, None, bn, None, 0, True))
+                h8 = None
+                saved += [a, h]  # the save list's layout, h now the pooled tensor
+                continue
             if not (gram and i + 1 == len(pairs) - 1) and _xfuse_ok(pairs[i + 1][0], a, q):
                 ss = xbn[i + 1] = bn_scale_shift(a, bn)
                 h, h8 = a, None
@@ -426,6 +440,7 @@ class BlockFn(torch.autograd.Function):
         block._T_done = False
         block._bnb_done = False
         ctx.block = block
+        ctx.pool = (pl[1], blur) if pl is not None else None
         ctx.xs = xs if xs is not x else None  # the pooled shortcut input of a D block
         ctx.xbn = xbn
         ctx.wg8 = wg8 or None
@@ -529,18 +544,25 @@ class BlockFn(torch.autograd.Function):
             if i > 0:
                 bn_prev = pairs[i - 1][1]
                 grouped = _conv._grouped(conv)
+                # an anti-aliased block's conv after the pool: its dgrad is sized to the pooled tensor, the pool's
+                # backward brings it to the BatchNorm's resolution, then the BN's reduce + apply pass
+                pooled = ctx.pool is not None and ctx.pool[0] == i - 1
+                full_hw = (acts[i - 1].shape[1], acts[i - 1].shape[2])
+                in_hw = (outs[i - 1].shape[1], outs[i - 1].shape[2]) if pooled else full_hw
                 # (a grouped conv's dgrad has no fused BN-backward epilogue: the BN before it takes the reduce pass)
-                fz = BNBwdFuse(acts[i - 1], bn_prev) if (fuse and not grouped) else None
+                fz = BNBwdFuse(acts[i - 1], bn_prev) if (fuse and not grouped and not pooled) else None
                 if grouped:
-                    dH = gconv_dgrad(dA, conv.wt_bf16, (acts[i - 1].shape[1], acts[i - 1].shape[2]), conv.stride,
+                    dH = gconv_dgrad(dA, conv.wt_bf16, in_hw, conv.stride,
                                      conv.groups)
                 elif isinstance(dA, GramBN):
                     dH = gram_dgrad(dA, conv, h_in, fz, Q=_gws(block, 3))
                     g_read = gram_wgrad(conv, dA, h_in, ctx.h2sum, G=_gws(block, 1), P=ctx.gram_P,
                                         bn=bn_l, T_out=_gws(block, 0), P_out=_gws(block, 4))  # issued now: it reads dout, which conv1's dgrad
                 else:                                    # accumulates into below
-                    dH = igemm_dgrad(dA, conv.wt_bf16, (acts[i - 1].shape[1], acts[i - 1].shape[2]), conv.stride,
+                    dH = igemm_dgrad(dA, conv.wt_bf16, in_hw, conv.stride,
                                      conv.padding, conv.kh, conv.kw, bnb=fz, fp8=_dg8(dA8, conv))
+                if pooled:
+                    dH = blurpool_bwd(dH, full_hw) if ctx.pool[1] else avgpool2_bwd(dH, full_hw)
                 if h_in is None:  # xfuse: the weight gradient applies the BN on its operand staging
                     h_in = (acts[i - 1], xbn[i])
                 dA_w, dA8_w = dA, dA8  # (dA8 is reassigned by the BN pass below: the copy that belongs to dA_w)

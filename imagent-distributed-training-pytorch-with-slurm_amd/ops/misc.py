@@ -6,6 +6,7 @@ import ctypes as C
 from typing import Optional, Sequence
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 from .conv import conv_out_size
@@ -235,6 +236,61 @@ class AvgPool2Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return avgpool2_bwd(dy.contiguous(), ctx.hw)
+
+
+def blurpool_torch(x: torch.Tensor) -> torch.Tensor:
+    """The definition of the anti-aliased archs' BlurPool on NCHW [N,C,H,W] (timm's ``aa_layer``; the torch
+    backend): depthwise ``[1,2,1]^T [1,2,1] / 16`` at stride 2 over the reflect-padded map."""
+    Cc = x.shape[1]
+    k = torch.tensor([1.0, 2.0, 1.0], device=x.device, dtype=x.dtype)
+    filt = (k[:, None] * k[None, :] / 16).expand(Cc, 1, 3, 3)
+    y = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), filt, stride=2, groups=Cc)
+    # keep the input's memory format, as the pools and the convs of the torch backend do: a 1x1 conv after the pool
+    # follows its input's format, and PyTorch's BatchNorm backward takes bf16 weights beside fp32 running statistics
+    # (autocast) only on its channels-last kernels
+    if x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous():
+        y = y.contiguous(memory_format=torch.channels_last)
+    return y
+
+
+def blurpool_fwd(x: torch.Tensor, ss: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """BlurPool on NHWC bf16 [N,H,W,C] (C % 8 == 0, H, W >= 2) -> [N,ceil(H/2),ceil(W/2),C] (blurpool.hip). With
+    ``ss`` (fp32 [2,C], :func:`ops.bn.bn_scale_shift`) the pooled values are ``relu(ss[0] * x + ss[1])``: BatchNorm +
+    ReLU + pool in one pass from the raw conv output, the normalised tensor is never written."""
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 4
+    N, H, W, Cc = x.shape
+    assert ss is None or (ss.dtype == torch.float32 and ss.is_contiguous() and tuple(ss.shape) == (2, Cc))
+    y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, Cc), device=x.device, dtype=torch.bfloat16)
+    _lib.check(_lib.kernels().imk_blurpool_fwd(x.data_ptr(), _lib.ptr(ss), y.data_ptr(), N, H, W, Cc,
+                                               _lib.stream_ptr()), "blurpool")
+    return y
+
+
+def blurpool_bwd(dy: torch.Tensor, in_hw) -> torch.Tensor:
+    """dx[N,H,W,C] of the plain :func:`blurpool_fwd`: the pool's transpose in gather form (a dense write of all of
+    dx, no memset, no atomics)."""
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and dy.dim() == 4
+    N, OH, OW, Cc = dy.shape
+    H, W = in_hw
+    assert OH == (H + 1) // 2 and OW == (W + 1) // 2, (tuple(dy.shape), in_hw)
+    dx = torch.empty((N, H, W, Cc), device=dy.device, dtype=torch.bfloat16)
+    _lib.check(_lib.kernels().imk_blurpool_bwd(dy.data_ptr(), dx.data_ptr(), N, H, W, Cc, _lib.stream_ptr()),
+               "blurpool bwd")
+    return dx
+
+
+class BlurPoolFn(torch.autograd.Function):
+    """The plain :func:`blurpool_fwd` as an autograd node (the per-op path and the stem; ops/block.py schedules the
+    fused BatchNorm + ReLU + pool itself)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (x.shape[1], x.shape[2])
+        return blurpool_fwd(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return blurpool_bwd(dy.contiguous(), ctx.hw)
 
 
 # ------------------------------------------------------------ loss+metrics

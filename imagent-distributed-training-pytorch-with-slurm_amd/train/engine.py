@@ -250,7 +250,10 @@ class Trainer:
         if getattr(a, "fp8_wgrad", False) and (a.dtype != "fp8" or a.kernels == "torch"):
             raise SystemExit("--fp8-wgrad needs --dtype fp8 --kernels hip (the fp8 weight gradient reads the 1-byte "
                              f"copies of the fp8 forward and dgrad): got --dtype {a.dtype} --kernels {a.kernels}")
-        from ..models.resnet import D_ARCHS, GROUPED_ARCHS, SE_ARCHS
+        from ..models.resnet import AA_ARCHS, D_ARCHS, GROUPED_ARCHS, SE_ARCHS
+        if a.arch in AA_ARCHS and a.dtype != "bf16" and a.kernels != "torch":
+            raise SystemExit(f"--arch {a.arch} with --dtype {a.dtype}: the anti-aliased archs' BlurPool / average pool "
+                             "have bf16 HIP kernels only; use --dtype bf16, or --kernels torch")
         if a.arch in D_ARCHS and a.dtype != "bf16" and a.kernels != "torch":
             raise SystemExit(f"--arch {a.arch} with --dtype {a.dtype}: the ResNet-D deep stem and average-pool shortcut "
                              "have bf16 HIP kernels only; use --dtype bf16, or --kernels torch")
